@@ -13,6 +13,11 @@ bucketed AUC). Nothing is skipped or cached across steps.
 
     python bench.py --gpus N --steps K --warmup W
     torchrun --nproc-per-node N bench.py --gpus N ...   (N > 1)
+
+A plain run does only that: set up, warm up, time the K steps, print one JSON line
+(``ms_per_step`` = wall time of the timed region / K). ``--dump-outputs DIR`` also writes
+what the timed steps computed (``dump_outputs`` below); ``--full`` is where any further
+measurement or check goes (none today).
 """
 from __future__ import annotations
 
@@ -967,6 +972,33 @@ def pipeline_merged(tr, B, N, seed, keys, labels, device, args, nprep=3, watch=N
     return iterate_native, True
 
 
+DUMP_MAX_ROWS = 2_000_000  # 5 arrays below: 2 M x (8 + 3 * 4) bytes = 40 MB
+
+
+def dump_outputs(path: str, sd: dict, prog: dict, max_rows: int = DUMP_MAX_ROWS) -> None:
+    """``--dump-outputs``: what the training run hands its caller after the last timed
+    step, as ``<name>.npy``: the model state of this rank's server shard
+    (``SparseLRTrainer.state_dict``: raw feature keys, sorted, with their w / z / n) and
+    the progress block behind the result line's ``train`` block (the timed steps and the
+    PSAMD_PRE_TIMING_ITERS untimed iterations right before them). More than ``max_rows``
+    entries: a fixed seeded sample of the sorted keys, so two builds given the same
+    arguments write the same rows."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    keys = sd["keys"].numpy().astype(np.int64)
+    order = np.argsort(keys, kind="stable")
+    if order.size > max_rows:
+        pick = np.random.default_rng(20240229).choice(order.size, max_rows, replace=False)
+        order = order[np.sort(pick)]
+    np.save(os.path.join(path, "keys.npy"), keys[order].astype(np.float64))  # (< 2^53: exact)
+    for name in ("w", "z", "n"):
+        np.save(os.path.join(path, name + ".npy"), sd[name].float().numpy()[order])
+    np.save(os.path.join(path, "progress.npy"),
+            np.array([prog[k] for k in ("examples", "loss", "accuracy", "auc", "nnz_w",
+                                        "updt_ratio")], dtype=np.float64))
+
+
 def spawn_ranks(n: int, argv: list[str] | None = None, script: str | None = None) -> int:
     """Re-launch this script as ``n`` ranks through torch.distributed.run (rendezvous on
     127.0.0.1, a free port) as a CHILD process, and return its exit code. Called
@@ -1151,6 +1183,15 @@ def main():
     ap.add_argument("--trace", default="",
                     help="write per-rank traffic/phase JSON here ({rank} substituted); "
                          "PSAMD_TRACE=1 adds roctx ranges + phase timers")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what they computed to DIR/<name>.npy "
+                         "(rank 0's shard): keys, w, z, n of the model state and the progress "
+                         "behind the line's train block; the same arguments give the same inputs in every run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline figure. "
+                         "There is none today: a plain run already only sets up, warms up, "
+                         "times the steps and prints the result line; anything further that "
+                         "this script learns to measure belongs behind this option")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.emulate_peers:
         # `python bench.py --gpus N`: fan out N ranks (one per GPU) before anything
@@ -1361,6 +1402,10 @@ def main():
     prog = tr.progress(reset=True)
     tr.check_ok()  # table full, localisation or exchange overflow: fail, do not report
     occ, nnz = tr.table.census()
+    if args.dump_outputs:
+        sd = tr.state_dict()  # (every rank: its flush is collective)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, sd, prog)
     emulated = comm.backend == "loopback" if hasattr(comm, "backend") else False
     n_ranks = 1 if emulated else G
     total_examples = n_ranks * B * args.steps

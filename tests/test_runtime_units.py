@@ -1,4 +1,5 @@
 import glob
+import os
 
 import numpy as np
 import pytest
@@ -22,6 +23,36 @@ def test_reference_confs_parse_and_roundtrip(path):
     c = AppConfig.parse(open(path).read())
     assert c.has("linear_method")
     assert AppConfig.parse(c.to_text()) == c
+
+
+GOLDEN_CONFS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "confs")
+
+
+@pytest.mark.parametrize("name", ["online_ftrl", "batch_darlin", "eval_model", "adagrad_sgd"])
+def test_golden_confs_parse_and_roundtrip(name):
+    """The project's own configs (tests/golden/confs): every block of the schema, comments,
+    repeated fields, nested messages and extensions; they need nothing outside the tree."""
+    with open(os.path.join(GOLDEN_CONFS, name + ".conf")) as f:
+        c = AppConfig.parse(f.read())
+    assert c.has("linear_method")
+    assert AppConfig.parse(c.to_text()) == c
+    lm = c.linear_method
+    if name == "online_ftrl":
+        assert c.app_name == "golden_online_ftrl" and len(lm.training_data.file) == 2
+        assert getattr(lm.penalty, "lambda") == [4.0, 0.5]
+        s = lm_to_sparse_lr(lm)
+        assert (s.algo, s.minibatch, s.tail_feature_freq, s.consistency) == ("ftrl", 4096, 2, "ssp:3")
+    elif name == "batch_darlin":
+        d = lm.darlin
+        assert d.prior_fea_group == [3, 11] and d.max_block_delay == 6
+        assert d.ext("delta_init_value") == 0.5 and d.ext("kkt_filter_threshold_ratio") == 10.0
+        assert (lm.training_data.range.begin, lm.training_data.range.end) == (0, 1048576)
+        assert d.init_w.type == "GAUSSIAN" and d.local_cache.format == "BIN"
+    elif name == "eval_model":
+        assert lm.model_input.hdfs.namenode == "nn.example:8020"
+        assert not lm.has("async_sgd") and not lm.has("darlin")
+    else:
+        assert lm.async_sgd.algo == "ADAGRAD" and lm.loss.type == "SQUARE"
 
 
 def test_textproto_extensions_and_errors():
