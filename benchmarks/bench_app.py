@@ -1,6 +1,6 @@
 """File-fed throughput of the GPU app (app/gpu.py): reference ``.conf`` + LIBSVM text
-files -> C++ parser threads -> pinned staging -> async host->HBM copies -> the HBM
-trainer. Generates the files first (not timed), then runs the app and reports
+files -> C++ parser threads (``--parser gpu``: the device text parser) -> pinned staging
+-> async host->HBM copies -> the HBM trainer. Generates the files first (not timed), then runs the app and reports
 examples/s of the whole run (parse + copy + train), next to the trainer-only rate of
 the same minibatches already in HBM.
 
@@ -130,6 +130,10 @@ def main():
                     help="1: run twice with a binary example cache (the first run parses the "
                          "text and writes the cache, the second streams the cache)")
     ap.add_argument("--io-threads", type=int, default=16)
+    ap.add_argument("--parser", default="cpu",
+                    help="text parser of the feeder: cpu, gpu or auto; a comma-separated list "
+                         "(cpu,gpu,cpu,gpu) runs one uncached text pass per entry over the "
+                         "same files, for alternating comparisons in one process")
     ap.add_argument("--report-steps", type=int, default=0,
                     help="progress line every this many steps on cached passes (0: 10 per pass)")
     a = ap.parse_args()
@@ -157,20 +161,28 @@ async_sgd {{ algo: FTRL minibatch: {a.minibatch} num_data_pass: 1 report_interva
     dev = torch.device("cuda")
     import types
 
+    parsers = a.parser.split(",")
+    if len(parsers) > 1:
+        a.cache = 0
     cache = os.path.join(d, "cache") if a.cache else "off"
     runs = []
     print(f"[bench_app] {a.rows} rows in {a.files} files ({mb:.0f} MB of text) in {gen_s:.1f} s",
           file=sys.stderr, flush=True)
-    for r in range(2 if a.cache else 1):
+    for r in range(2 if a.cache else len(parsers)):
         flags = types.SimpleNamespace(
+            parser=parsers[r % len(parsers)],
             num_features=1e8, max_nnz_per_example=160 if a.kind == "rcv1" else 39,
             num_threads=a.threads, device="cuda", seed=0, table_capacity=1 << 27, quiet=False,
             data_cache=cache, io_threads=a.io_threads, report_steps=a.report_steps)
         res = run_async_sgd(lm, LocalComm(dev), dev, flags)
         tr = res["trainer"]
         print(f"[bench_app] run {r}: {res['examples'] / res['seconds'] / 1e6:.2f} M ex/s "
-              f"({'cache' if res['cached_passes'] else 'text'})", file=sys.stderr, flush=True)
+              f"({'cache' if res['cached_passes'] else 'text, parser ' + res['parser']})",
+              file=sys.stderr, flush=True)
         runs.append({"source": "cache" if res["cached_passes"] else "text",
+                     "parser": res["parser"], "text_chunks": res["text_chunks"],
+                     "deferred_chunks": res["deferred_chunks"],
+                     "text_mb_per_s": None if res["cached_passes"] else mb / res["seconds"],
                      "rows": res["examples"], "steps": res["steps"],
                      "seconds": round(res["seconds"], 3),
                      "examples_per_s": res["examples"] / res["seconds"],

@@ -66,7 +66,9 @@ def build_hipops(jobs: int = 8, verbose: bool = False) -> Path:
     src_dir = CSRC / "hip"
     out_dir = BUILD / "hip"
     out_dir.mkdir(parents=True, exist_ok=True)
-    headers = sorted(src_dir.glob("*.cuh")) + sorted(src_dir.glob("*.h"))
+    # (textparse.hip includes the scanners it shares with the host runtime)
+    headers = sorted(src_dir.glob("*.cuh")) + sorted(src_dir.glob("*.h")) + \
+        [CSRC / "core" / "textnum.h"]
     common = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", str(src_dir),
               "-Wno-unused-result", "-Wno-deprecated-declarations"]
     jobs_list = []

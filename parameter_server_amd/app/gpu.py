@@ -58,6 +58,9 @@ def _flags(argv):
     # (Criteo-shaped 8 M rows, B = 65,536: 8 threads 52-64 M ex/s, 16 threads 86 M,
     # profiles/r6_app_cache.log)
     ap.add_argument("-io_threads", "--io_threads", type=int, default=16)
+    # text parser of the file-fed path: "cpu" (C++ parser threads), "gpu" (LIBSVM / CRITEO
+    # text parsed by HIP kernels, data/feeder.py), "auto" (gpu where it applies)
+    ap.add_argument("-parser", "--parser", choices=("cpu", "gpu", "auto"), default="cpu")
     # progress lines every this many steps when the step count is agreed up front (a
     # fully cached multi-rank run); 0 = 20 lines per run
     ap.add_argument("-report_steps", "--report_steps", type=int, default=0)
@@ -119,7 +122,8 @@ def run_async_sgd(lm, comm, device, flags, printer=None) -> dict:
                           ignore_slot=True,
                           hadoop_home=td.hdfs.home if td.has("hdfs") else "",
                           max_lines_per_file=td.max_num_lines_per_file,
-                          cache_dir=cache_dir, io_threads=getattr(flags, "io_threads", 16))
+                          cache_dir=cache_dir, io_threads=getattr(flags, "io_threads", 16),
+                          parser=getattr(flags, "parser", "cpu"))
     interval = max(1, int(sgd.report_interval))
     printer = printer or (ProgressPrinter() if rank == 0 and not flags.quiet else None)
     t0 = last = time.time()
@@ -194,6 +198,8 @@ def run_async_sgd(lm, comm, device, flags, printer=None) -> dict:
     out = {"examples": feeder.num_examples, "steps": steps, "idle_steps": idle, "seconds": dt,
            "progress": p if p["examples"] else last_p, "trainer": tr, "h2d_bytes": feeder.bytes_h2d,
            "text_passes": feeder.text_passes, "cached_passes": feeder.cached_passes,
+           "parser": feeder.parser, "text_chunks": feeder.text_chunks,
+           "deferred_chunks": feeder.deferred_chunks,
            "agreed_steps": agreed, "host_feed_wait_s": t_feed, "host_step_issue_s": t_step}
     if tmp_cache:
         import shutil

@@ -2,8 +2,12 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
+#include <type_traits>
+
 #include "data.h"
 #include "module_parts.h"
+#include "textnum.h"
 
 namespace py = pybind11;
 
@@ -108,6 +112,44 @@ void register_data(py::module_& m) {
     std::vector<py::bytes> out;
     for (auto& r : recordio_unpack(data)) out.emplace_back(r);
     return out;
+  });
+  // Test-only batch entry points of the scanners the GPU text parser shares with the
+  // host (csrc/core/textnum.h): (values, status codes) per token.
+  auto scan_batch = [](const std::vector<py::bytes>& toks, auto* proto, auto&& fn) {
+    using T = std::remove_pointer_t<decltype(proto)>;
+    py::array_t<T> vals((py::ssize_t)toks.size());
+    py::array_t<int32_t> st((py::ssize_t)toks.size());
+    T* v = vals.mutable_data();
+    int32_t* s = st.mutable_data();
+    for (size_t i = 0; i < toks.size(); ++i) {
+      char* ptr = nullptr;
+      Py_ssize_t len = 0;
+      if (PyBytes_AsStringAndSize(toks[i].ptr(), &ptr, &len) != 0) throw py::error_already_set();
+      v[i] = T(0);
+      s[i] = fn((const uint8_t*)ptr, (int)std::min<Py_ssize_t>(len, 1 << 20), &v[i]);
+    }
+    return py::make_tuple(vals, st);
+  };
+  m.def("textnum_f32", [scan_batch](const std::vector<py::bytes>& t) {
+    return scan_batch(t, (float*)nullptr, textnum::scan_f32);
+  });
+  m.def("textnum_u64", [scan_batch](const std::vector<py::bytes>& t) {
+    return scan_batch(t, (uint64_t*)nullptr, textnum::scan_u64);
+  });
+  m.def("textnum_i64", [scan_batch](const std::vector<py::bytes>& t) {
+    return scan_batch(t, (int64_t*)nullptr, textnum::scan_i64);
+  });
+  m.def("textnum_hex", [scan_batch](const std::vector<py::bytes>& t) {
+    return scan_batch(t, (uint64_t*)nullptr, textnum::scan_hex);
+  });
+  m.def("textnum_criteo_bucket", [](py::array_t<int64_t, py::array::c_style> v) {
+    py::array_t<uint64_t> ids(v.size());
+    py::array_t<int32_t> st(v.size());
+    for (py::ssize_t i = 0; i < v.size(); ++i) {
+      ids.mutable_data()[i] = 0;
+      st.mutable_data()[i] = textnum::criteo_bucket(v.data()[i], &ids.mutable_data()[i]);
+    }
+    return py::make_tuple(ids, st);
   });
   m.attr("RECORDIO_MAGIC") = kRecordIOMagic;
 }

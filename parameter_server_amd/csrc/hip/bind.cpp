@@ -264,6 +264,13 @@ void spmv(bool, const int64_t*, const void*, int, const void*, int, int64_t, int
 // gemm.hip
 void gemm_bf16(bool, bool, const void*, int, const void*, int, int, int, int, int, const float*,
                const void*, int, void*, int, float*, int, float, int, float*, hipStream_t);
+// textparse.hip
+int64_t textparse_span();
+int64_t textparse_work_words(int64_t);
+void textparse(const uint8_t*, int64_t, int, uint64_t, int64_t, int64_t, float*, int64_t, int64_t*,
+               int64_t, uint64_t*, float*, int64_t, int32_t*, int32_t*, hipStream_t);
+void textparse_rebase(const int64_t*, int64_t*, int64_t, int64_t, hipStream_t);
+void textparse_seg_nonunit(const float*, int64_t, const int64_t*, int, int32_t*, hipStream_t);
 }  // namespace psamd
 
 using at::Tensor;
@@ -1896,6 +1903,48 @@ PYBIND11_MODULE(_hipops, m) {
     auto out = torch::zeros({2}, slots.options().dtype(at::kLong));
     psamd::kv_census(slots.data_ptr(), cap, ptr<unsigned long long>(out), cur_stream());
     return out;
+  });
+
+  // ---------------- text parsing ----------------
+  m.def("textparse_span", [] { return psamd::textparse_span(); });
+  m.def("textparse_work_words", [](int64_t n) { return psamd::textparse_work_words(n); });
+  m.def("textparse", [](Tensor text, int64_t n, int fmt, uint64_t hash_mod, int64_t row0,
+                        int64_t nnz0, Tensor labels, Tensor row_ptr, Tensor keys,
+                        optional<Tensor> vals, Tensor hdr, Tensor work) {
+    chk(text, at::kByte, "text");
+    chk(labels, at::kFloat, "labels");
+    chk(row_ptr, at::kLong, "row_ptr");
+    chk(keys, at::kLong, "keys");
+    chk(hdr, at::kInt, "hdr");
+    chk(work, at::kInt, "work");
+    float* vp = optr<float>(vals, at::kFloat, "vals");
+    check(n >= 1 && n <= text.numel(), "textparse: n outside the text buffer");
+    check(row0 >= 0 && nnz0 >= 0 && row0 < row_ptr.numel(), "textparse: bad base offsets");
+    check(hdr.numel() >= 8, "textparse: header needs 8 words");
+    check(work.numel() >= psamd::textparse_work_words(n), "textparse: work buffer too small");
+    int64_t cap_nnz = keys.numel();
+    if (vp) cap_nnz = std::min<int64_t>(cap_nnz, vals->numel());
+    psamd::textparse(ptr<uint8_t>(text), n, fmt, hash_mod, row0, nnz0, ptr<float>(labels),
+                     labels.numel(), ptr<int64_t>(row_ptr), row_ptr.numel(), ptr<uint64_t>(keys),
+                     vp, cap_nnz, ptr<int32_t>(hdr), ptr<int32_t>(work), cur_stream());
+  }, py::arg("text"), py::arg("n"), py::arg("fmt"), py::arg("hash_mod"), py::arg("row0"),
+     py::arg("nnz0"), py::arg("labels"), py::arg("row_ptr"), py::arg("keys"), py::arg("vals"),
+     py::arg("hdr"), py::arg("work"));
+  m.def("textparse_rebase", [](Tensor in, Tensor out, int64_t n, int64_t delta) {
+    chk(in, at::kLong, "in");
+    chk(out, at::kLong, "out");
+    check(n >= 0 && in.numel() >= n && out.numel() >= n, "textparse_rebase: buffers too small");
+    psamd::textparse_rebase(ptr<int64_t>(in), ptr<int64_t>(out), n, delta, cur_stream());
+  });
+  m.def("textparse_seg_nonunit", [](Tensor vals, Tensor bounds, Tensor flags) {
+    chk(vals, at::kFloat, "vals");
+    chk(bounds, at::kLong, "bounds");
+    chk(flags, at::kInt, "flags");
+    const int64_t nseg = bounds.numel() - 1;
+    check(nseg >= 0 && nseg < (1 << 30) && flags.numel() >= nseg,
+          "textparse_seg_nonunit: flags too small");
+    psamd::textparse_seg_nonunit(ptr<float>(vals), vals.numel(), ptr<int64_t>(bounds), (int)nseg,
+                                 ptr<int32_t>(flags), cur_stream());
   });
 
   // ---------------- localisation ----------------

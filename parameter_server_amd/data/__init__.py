@@ -134,7 +134,13 @@ def merge_example_info(infos: list[dict]) -> dict:
 class StreamReader:
     """Minibatch stream over a file list (reference StreamReader::readMatrices),
     with a producer thread bounded by ``data_buf`` MB (ProducerConsumer,
-    src/util/producer_consumer.h)."""
+    src/util/producer_consumer.h).
+
+    This reader always parses with the C++ parser (``parse_text``). The device feeder
+    (data/feeder.py) has a second parser for LIBSVM / CRITEO text, ``parser="gpu"``: HIP
+    kernels over chunks of raw bytes in HBM, with this parser as the fallback for chunks
+    they decline; it cuts minibatches by the rules of ``_cut`` below, so both yield the
+    same stream of minibatches."""
 
     def __init__(self, files, fmt="LIBSVM", minibatch=1000, *, ignore_slot=False,
                  data_buf_mb=1000, hash_mod=0, passes=1, shuffle=False, seed=0, hadoop_home="",

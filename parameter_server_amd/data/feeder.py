@@ -24,10 +24,24 @@ device slots; ``release(batch)`` after the step that reads it was issued):
   GPU-side wait). The number of minibatches is known up front (``planned_batches``), so
   a multi-rank app agrees on its step count once instead of every step.
 
+The text source has two parsers (``parser=``). ``"cpu"`` (the default) is the path above.
+``"gpu"`` parses LIBSVM / CRITEO text on the device (ops/textparse.py, textparse.hip):
+reader threads read each file straight into pinned chunk buffers of ``chunk_bytes``, cut at
+the last newline; a chunk is copied to HBM on the copy stream and parsed on a parse stream
+into one of a ring of device output buffers; minibatches are slices of the parsed chunk
+(same cut rules, so the stream of minibatches is the CPU parser's, including minibatches
+that span files: rows left over are carried to the front of the next chunk's output by a
+device-to-device copy). A chunk the kernels decline (a malformed or ``#`` line, a number
+outside their exact domain, a line longer than a chunk) is parsed by the CPU parser from
+the pinned copy of the same bytes (``deferred_chunks``). Other formats,
+``max_lines_per_file > 0`` and ``device="cpu"`` use the CPU parser whatever ``parser``
+says; ``"auto"`` picks the GPU parser where it applies.
+
 With ``device="cpu"`` the same interface yields CPU tensors (no pinned memory, no
 streams): the CPU test path of the GPU app."""
 from __future__ import annotations
 
+import io
 import os
 import queue
 import random
@@ -37,8 +51,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import TEXT_FORMATS, StreamReader
+from . import TEXT_FORMATS, ExampleBatch, StreamReader, read_file
 from . import bincache
+from ..ops import textparse
 
 
 @dataclass
@@ -53,12 +68,75 @@ class DeviceBatch:
     width: int = 0               # > 0: every row has exactly this many features
 
 
+def _last_newline(arr: np.ndarray, n: int) -> int:
+    """Index of the last newline byte in arr[:n], or -1 (searched backwards in windows)."""
+    hi = n
+    while hi > 0:
+        lo = max(0, hi - (1 << 16))
+        hit = np.flatnonzero(arr[lo:hi] == 10)
+        if hit.size:
+            return lo + int(hit[-1])
+        hi = lo
+    return -1
+
+
+class _ChunkSet(textparse.TextParseBuffers):
+    """One output set of the device-parser path: the arrays of a parsed chunk, the
+    per-minibatch row offsets cut out of it, and the bookkeeping of its reuse -- a set is
+    parsed into again only when every minibatch sliced from it was released (a host-side
+    count) and behind the last of those steps on the GPU (``released``)."""
+
+    def __init__(self, cap_rows, cap_nnz, device, text_bytes):
+        super().__init__(cap_rows, cap_nnz, device, text_bytes)
+        self.parsed = torch.cuda.Event()    # the chunk's parse and row-offset kernels
+        self.released = torch.cuda.Event()  # the last step that read a slice of it
+        self._cond = threading.Condition()
+        self._held = 0
+        self._mb = torch.empty(2 * self.cap_rows + 2, dtype=torch.int64, device=device)
+        self._mb_used = 0
+        self._keep = []  # tensors replaced while slices of them may still be read
+
+    def hold(self):
+        with self._cond:
+            self._held += 1
+
+    def unhold(self):
+        with self._cond:
+            self._held -= 1
+            self._cond.notify_all()
+
+    def acquire(self, stream):
+        with self._cond:
+            while self._held:
+                self._cond.wait()
+        stream.wait_event(self.released)
+        self._keep.clear()
+        self._mb_used = 0
+
+    def grow(self, rows, nnz, keep_rows=0, keep_nnz=0):
+        self._keep.append((self.labels, self.row_ptr, self.keys, self.vals))
+        super().grow(rows, nnz, keep_rows, keep_nnz)
+
+    def mb_row_ptr(self, n: int) -> torch.Tensor:
+        if self._mb_used + n > self._mb.numel():
+            self._keep.append(self._mb)
+            self._mb = torch.empty(max(self._mb.numel(), 2 * n), dtype=torch.int64,
+                                   device=self.device)
+            self._mb_used = 0
+        v = self._mb[self._mb_used:self._mb_used + n]
+        self._mb_used += n
+        return v
+
+
 class DeviceFeeder:
     def __init__(self, files, fmt: str, minibatch: int, max_nnz: int, device, *,
                  num_features: int = 0, passes: int = 1, shuffle: bool = False, seed: int = 0,
                  data_buf_mb: int = 1000, nthreads: int = 4, depth: int = 3,
                  ignore_slot: bool = True, hadoop_home: str = "", max_lines_per_file: int = -1,
-                 cache_dir: str | None = None, io_threads: int = 4):
+                 cache_dir: str | None = None, io_threads: int = 4, parser: str = "cpu",
+                 chunk_bytes: int = 32 << 20):
+        if parser not in ("cpu", "gpu", "auto"):
+            raise ValueError(f"parser must be 'cpu', 'gpu' or 'auto', not {parser!r}")
         self.device = torch.device(device)
         self.gpu = self.device.type == "cuda"
         self.files = list(files)
@@ -83,6 +161,14 @@ class DeviceFeeder:
         self.text_passes = 0    # passes that parsed text
         self.cached_passes = 0  # passes streamed from the binary cache
         self._fmt_id = TEXT_FORMATS.get(fmt, 0) if isinstance(fmt, str) else int(fmt)
+        # the parser in use: the device parser needs a GPU, a format it knows and whole files
+        self.parser = "gpu" if (parser != "cpu" and self.gpu and max_lines_per_file <= 0
+                                and textparse.supported(self._fmt_id)) else "cpu"
+        self.chunk_bytes = max(1024, int(chunk_bytes))
+        self.text_chunks = 0      # chunks of text handed to the device parser
+        self.deferred_chunks = 0  # of them: parsed by the CPU parser after all
+        self.bytes_text = 0       # bytes of text parsed through the device path
+        self._tp = None           # device-parser state (allocated by the first text pass)
         # the pass order of the files (StreamReader's per-pass shuffle)
         self._orders = []
         for _ in range(self.passes):
@@ -266,8 +352,8 @@ class DeviceFeeder:
 
     def _iter_text(self, order):
         q: queue.Queue = queue.Queue(maxsize=self.depth)
-        th = threading.Thread(target=self._stage_text, args=(order, q), daemon=True,
-                              name="device-feeder")
+        stage = self._stage_text_gpu if self.parser == "gpu" else self._stage_text
+        th = threading.Thread(target=stage, args=(order, q), daemon=True, name="device-feeder")
         th.start()
         while True:
             b = q.get()
@@ -276,9 +362,274 @@ class DeviceFeeder:
                 if self._error is not None:
                     raise self._error
                 return
-            if self.gpu:  # the step's stream waits for the batch's host->HBM copy
+            if self.gpu and b.slot >= 0:  # the step's stream waits for the host->HBM copy
                 torch.cuda.current_stream(self.device).wait_event(self._h2d_done[b.slot])
+            elif self.gpu and b.slot <= -2:  # ... or for the parse of the batch's chunk
+                torch.cuda.current_stream(self.device).wait_event(
+                    self._tp["sets"][-2 - b.slot].parsed)
             yield b
+
+    # ------------------------------------------------------------ text staging (device parser)
+    def _tp_state(self):
+        """Buffers of the device-parser path: pinned chunk buffers, two device text
+        buffers, a ring of output sets sized from ``chunk_bytes``, the parse stream."""
+        if self._tp is None:
+            C, dev = self.chunk_bytes, self.device
+            # (a feature is >= 4 bytes of text, a row >= 4 in practice; denser chunks are
+            # deferred and their set grows)
+            cap_rows, cap_nnz = C // 4 + self.minibatch + 1, C // 4 + self.max_nnz + 1
+            self._tp = dict(
+                pin=[torch.empty(C, dtype=torch.uint8, pin_memory=True) for _ in range(3)],
+                text=[torch.empty(C, dtype=torch.uint8, device=dev) for _ in range(2)],
+                sets=[_ChunkSet(cap_rows, cap_nnz, dev, C) for _ in range(3)],
+                stream=torch.cuda.Stream(dev), nchunk=0, nset=0)
+        return self._tp
+
+    def _read_chunks(self, order, q: queue.Queue, free_pin: queue.Queue):
+        """Reader thread: ("chunk", pinned index, bytes, file) pieces of whole lines,
+        ("big", bytes, file) for a line longer than a chunk, ("eof", file), then None."""
+        try:
+            C, pin = self.chunk_bytes, self._tp["pin"]
+            for f in order:
+                plain = (not self.hadoop_home and not f.startswith("hdfs://")
+                         and not f.endswith(".gz"))
+                src = open(f, "rb", buffering=0) if plain else \
+                    io.BytesIO(read_file(f, self.hadoop_home))
+                with src:
+                    tail, eof = b"", False
+                    while not eof:
+                        i = free_pin.get()
+                        arr = pin[i].numpy()
+                        mv = memoryview(arr)
+                        have = len(tail)
+                        mv[:have] = tail
+                        tail = b""
+                        while have < C:
+                            got = src.readinto(mv[have:C])
+                            if not got:
+                                eof = True
+                                break
+                            have += got
+                        if have == 0:
+                            free_pin.put(i)
+                            break
+                        cut = have
+                        if not eof:
+                            cut = _last_newline(arr, have) + 1
+                            if cut == 0:  # no newline in a whole chunk: read on to the line's end
+                                big = bytearray(mv[:have])
+                                free_pin.put(i)
+                                while True:
+                                    piece = src.read(min(C, 1 << 20))
+                                    if not piece:
+                                        eof = True
+                                        break
+                                    k = piece.find(b"\n")
+                                    if k >= 0:
+                                        big += piece[:k + 1]
+                                        tail = piece[k + 1:]
+                                        break
+                                    big += piece
+                                q.put(("big", bytes(big), f))
+                                continue
+                            tail = bytes(mv[cut:have])
+                        q.put(("chunk", i, cut, f))
+                q.put(("eof", f))
+            q.put(None)
+        except BaseException as e:  # noqa: BLE001  (re-raised by the staging thread)
+            q.put(e)
+
+    def _stage_text_gpu(self, order, out_q: queue.Queue):
+        try:
+            tp = self._tp_state()
+            cs, ps = self._copy_stream, tp["stream"]
+            free_pin: queue.Queue = queue.Queue()
+            for i in range(len(tp["pin"])):
+                free_pin.put(i)
+            q: queue.Queue = queue.Queue()
+            threading.Thread(target=self._read_chunks, args=(order, q, free_pin), daemon=True,
+                             name="text-reader").start()
+
+            def fetch():
+                """The reader's next item; a chunk's host->HBM copy is issued at once (it
+                overlaps the parse of the chunk before it)."""
+                it = q.get()
+                if isinstance(it, BaseException):
+                    raise it
+                if it is not None and it[0] == "chunk":
+                    _, i, n, f = it
+                    d = tp["text"][tp["nchunk"] % 2]  # (its last parse was synchronised)
+                    tp["nchunk"] += 1
+                    ev = torch.cuda.Event()
+                    with torch.cuda.stream(cs):
+                        d[:n].copy_(tp["pin"][i][:n], non_blocking=True)
+                        ev.record(cs)
+                    self.bytes_h2d += n
+                    it = ("chunk", i, n, f, d, ev)
+                return it
+
+            libsvm = self._fmt_id == TEXT_FORMATS["LIBSVM"]
+            carry = None     # rows parsed but not yet cut into a minibatch
+            pieces = []      # host copies of the current file's arrays (cache_dir)
+            nxt = fetch()
+            while nxt is not None:
+                cur, nxt = nxt, None
+                if cur[0] == "eof":
+                    if self.cache_dir:
+                        self._write_cache_pieces(cur[1], pieces)
+                    pieces = []
+                    nxt = fetch()
+                    continue
+                nxt = fetch()
+                st = tp["sets"][tp["nset"] % len(tp["sets"])]
+                tp["nset"] += 1
+                st.acquire(ps)
+                with torch.cuda.stream(ps):
+                    r0 = n0 = 0
+                    if carry is not None:  # leftover rows go in front of this chunk's
+                        P, a = carry["set"], carry["a"]
+                        r0, na = carry["Rn"] - a, carry["nnz_at"](a)
+                        n0 = carry["N"] - na
+                        st.grow(r0 + 1, n0 + 1)
+                        st.labels[:r0].copy_(P.labels[a:a + r0])
+                        st.keys[:n0].copy_(P.keys[na:na + n0])
+                        if libsvm:
+                            st.vals[:n0].copy_(P.vals[na:na + n0])
+                        textparse.rebase_row_ptr(P.row_ptr[a:a + r0 + 1], st.row_ptr, r0 + 1, na)
+                        P.unhold()
+                    self.text_chunks += 1
+                    if cur[0] == "chunk":
+                        _, i, n, f, d, ev = cur
+                        ps.wait_event(ev)
+                        res = textparse.parse_text_device(d, self._fmt_id, self.num_features,
+                                                          out=st, row0=r0, nnz0=n0, n=n,
+                                                          host=tp["pin"][i])
+                        free_pin.put(i)
+                    else:  # a line longer than a chunk: the CPU parser's
+                        n = len(cur[1])
+                        res = textparse._store_host(
+                            textparse._host_parse(cur[1], self._fmt_id, self.num_features), st,
+                            r0, n0, self._fmt_id, True)
+                    self.bytes_text += n
+                    self.deferred_chunks += bool(res.deferred)
+                    Rn, N = r0 + res.rows, n0 + res.nnz
+                    if res.rows == 0:
+                        W = carry["W"] if carry is not None else 0
+                    elif r0 == 0:
+                        W = res.width
+                    else:
+                        W = res.width if res.width == carry["W"] else 0
+                    rp = None if W else st.row_ptr[:Rn + 1].cpu().numpy()
+                    if self.cache_dir:
+                        pieces.append(self._host_piece(st, res, r0, n0, W, rp, libsvm))
+                    nonunit = libsvm and (res.vals is not None or
+                                          (carry is not None and carry["nonunit"]))
+                    carry = self._cut_chunk(st, 0, Rn, N, W, rp, nonunit, False, out_q, ps)
+            if carry is not None:  # the rows left at the end of the pass
+                with torch.cuda.stream(ps):
+                    self._cut_chunk(carry["set"], carry["a"], carry["Rn"], carry["N"], carry["W0"],
+                                    carry["rp"], carry["nonunit"], True, out_q, ps)
+                carry["set"].unhold()
+        except BaseException as e:  # noqa: BLE001  (re-raised by the consumer)
+            self._error = e
+        finally:
+            out_q.put(None)
+
+    def _cut_chunk(self, st, a, Rn, N, W, rp, nonunit, final, out_q, ps):
+        """Minibatches out of rows [a, Rn) of a parsed set (StreamReader._cut rules: at most
+        ``minibatch`` rows and ``max_nnz`` features; nothing is cut while more rows could
+        still join a minibatch, unless ``final``). W > 0: every row has W features; else
+        ``rp`` is the set's row_ptr on the host. Returns the carry (rows left) or None."""
+        mb, cap = self.minibatch, self.max_nnz
+
+        def nnz_at(j):
+            return j * W if W else int(rp[j])
+
+        cuts = []
+        while a < Rn:
+            have = Rn - a
+            if not final and have < mb and not (cap and N - nnz_at(a) > cap):
+                break
+            b = a + min(mb, have)
+            if cap and nnz_at(b) - nnz_at(a) > cap:
+                if W:
+                    b = a + cap // W
+                else:
+                    b = a + int(np.searchsorted(rp[a:Rn + 1], rp[a] + cap, side="right")) - 1
+                if b - a < 1:
+                    raise ValueError(f"an example has {nnz_at(a + 1) - nnz_at(a)} features > "
+                                     f"the per-minibatch capacity {cap}")
+            cuts.append((a, b))
+            a = b
+        left = None
+        if a < Rn:
+            st.hold()
+            wl = W
+            if not W:
+                d = np.diff(rp[a:Rn + 1])
+                wl = int(d[0]) if d[0] > 0 and bool((d == d[0]).all()) else 0
+            # (W: the width of the rows left, for the chunk they join; W0 / rp index this set)
+            left = dict(set=st, a=a, Rn=Rn, N=N, W=wl, W0=W, rp=rp, nnz_at=nnz_at,
+                        nonunit=nonunit)
+        if not cuts and left is None:
+            return None
+        flags = None
+        if nonunit:  # which minibatches (and the rest) hold a value other than 1
+            bounds = [nnz_at(c[0]) for c in cuts] + [nnz_at(a), N]
+            flags = textparse.segments_valued(
+                st.vals, torch.tensor(bounds, dtype=torch.int64).to(st.device)).cpu().tolist()
+            if left is not None:
+                left["nonunit"] = bool(flags[-1])
+        slot = -2 - self._tp["sets"].index(st)
+        out = []
+        for k, (x, y) in enumerate(cuts):
+            s, e = nnz_at(x), nnz_at(y)
+            B, n = y - x, e - s
+            if W:
+                width = W
+            else:
+                d, w = rp[x + 1:y + 1] - rp[x:y], n // B
+                width = w if n % B == 0 and bool((d == w).all()) else 0
+            row_ptr = None
+            if not width:
+                row_ptr = st.mb_row_ptr(B + 1)
+                textparse.rebase_row_ptr(st.row_ptr[x:y + 1], row_ptr, B + 1, s)
+            vals = st.vals[s:e] if flags is not None and flags[k] else None
+            out.append(DeviceBatch(st.keys[s:e], st.labels[x:y], row_ptr, vals, B, n, slot, width))
+        st.parsed.record(ps)
+        for b in out:
+            st.hold()
+        for b in out:
+            out_q.put(b)
+        return left
+
+    def _host_piece(self, st, res, r0, n0, W, rp, libsvm):
+        """Host copies of the rows a chunk added (for the file's binary cache)."""
+        rows, nnz = res.rows, res.nnz
+        lrp = np.arange(0, (rows + 1) * W, W, dtype=np.int64) if W else rp[r0:r0 + rows + 1] - n0
+        return (st.labels[r0:r0 + rows].cpu().numpy(), lrp,
+                st.keys[n0:n0 + nnz].cpu().numpy().view(np.uint64),
+                st.vals[n0:n0 + nnz].cpu().numpy() if libsvm else None)
+
+    def _write_cache_pieces(self, f: str, pieces):
+        """One file's parsed arrays as its binary cache (as StreamReader._write_cache)."""
+        cf = bincache.open_valid(f, self.cache_dir, self.fmt, self._fmt_id, self.num_features,
+                                 self.ignore_slot)
+        if cf is not None:
+            cf.close()
+            return
+        rp, off = [np.zeros(1, np.int64)], 0
+        for p in pieces:
+            rp.append(p[1][1:] + off)
+            off += int(p[1][-1])
+        cat = (lambda k, dt: np.concatenate([p[k] for p in pieces]) if pieces
+               else np.zeros(0, dt))
+        vals = None if not pieces or pieces[0][3] is None else cat(3, np.float32)
+        b = ExampleBatch(cat(0, np.float32), np.concatenate(rp), cat(2, np.uint64), vals,
+                         np.zeros(0, np.int32))
+        bincache.write_cache(bincache.cache_path(self.cache_dir, f, self.fmt, self.num_features,
+                                                 self.ignore_slot), b, src=f, fmt_id=self._fmt_id,
+                             hash_mod=self.num_features, ignore_slot=self.ignore_slot)
 
     # ------------------------------------------------------------ cached streaming
     def _run_props(self):
@@ -444,3 +795,7 @@ class DeviceFeeder:
             self._released[b.slot].record(torch.cuda.current_stream(self.device))
             if self._mode == "text":  # (cached streaming assigns slots round-robin)
                 self._free.put(b.slot)
+        elif self.gpu and b.slot <= -2:  # a slice of a parsed chunk (device parser)
+            st = self._tp["sets"][-2 - b.slot]
+            st.released.record(torch.cuda.current_stream(self.device))
+            st.unhold()
