@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What bounds the flat step kernel (csrc/hip/tploc.hip tpf_step / tpf_step2)? Times, on
+"""What bounds the flat step kernel (csrc/hip/tploc.hip tpf_step)? Times, on
 one localised 65,536 x 39 Criteo-shaped minibatch after a few training steps: the pull
 half, the update half, both in one launch, an empty launch (all counts 0), and the
 compact path's kv_resolve of the same distinct keys, for table capacities 2^22 / 2^26 /
@@ -67,17 +67,14 @@ for lg in (22, 26, 31):
               *tr.rule.args(), tr.stats)
     zero = tuple(torch.zeros_like(x) if i == 0 else x for i, x in enumerate(loc.bufs))
     row = {"table_log2": lg}
-    for v1 in ("1", "0"):
-        os.environ["PSAMD_TPF_STEP2"] = "0" if v1 == "1" else "1"
-        tag = "v1" if v1 == "1" else "v2"
-        row[f"pull_{tag}"] = timeit_list(lambda L: L.add_tpf_step(
-            n, bits, None, None, loc.bufs, loc.w_ent, *common, None, None, None))
-        row[f"update_{tag}"] = timeit_list(lambda L: L.add_tpf_step(
-            n, bits, loc.bufs, loc.psum, None, None, *common, None, None, None))
-        row[f"both_{tag}"] = timeit_list(lambda L: L.add_tpf_step(
-            n, bits, loc.bufs, loc.psum, loc.bufs, loc.w_ent, *common, None, None, None))
-        row[f"empty_{tag}"] = timeit_list(lambda L: L.add_tpf_step(
-            n, bits, zero, loc.psum, zero, loc.w_ent, *common, None, None, None))
+    row["pull"] = timeit_list(lambda L: L.add_tpf_step(
+        n, bits, None, None, loc.bufs, loc.w_ent, *common, None, None, None))
+    row["update"] = timeit_list(lambda L: L.add_tpf_step(
+        n, bits, loc.bufs, loc.psum, None, None, *common, None, None, None))
+    row["both"] = timeit_list(lambda L: L.add_tpf_step(
+        n, bits, loc.bufs, loc.psum, loc.bufs, loc.w_ent, *common, None, None, None))
+    row["empty"] = timeit_list(lambda L: L.add_tpf_step(
+        n, bits, zero, loc.psum, zero, loc.w_ent, *common, None, None, None))
     row["fwd_bwd"] = timeit_list(lambda L: L.add_tp_fwd_bwd(
         loc.rep, loc.dcnt, None, n, 39, None, loc.w_ent, lab, B, 0, tr.coef[:B], tr.metrics,
         tr.hist, 2048, loc.psum, None, None, None, None, False))

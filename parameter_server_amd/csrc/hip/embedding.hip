@@ -324,10 +324,7 @@ emb_grad_seg_kernel(const int32_t* __restrict__ pos_s, const int32_t* __restrict
 // Segments crossing run boundaries: the run where segment u starts (its last
 // piece continues to the right) sums its slot-1 partial and the slot-0 partials
 // of the following runs up to the segment's end, in order.
-// (A hot key's segment spans up to B / 64 runs: its partials are loaded kB at a time,
-// clamped in range and unconditionally, so one wave has kB loads in flight instead of
-// a round trip per run.)
-template <int C, int kB>
+template <int C>
 __global__ void __launch_bounds__(256)
 emb_grad_cross_kernel(const int32_t* __restrict__ segid, const int32_t* __restrict__ seg_start,
                       int64_t u_cap, int64_t nnz, const float* __restrict__ part,
@@ -351,39 +348,15 @@ emb_grad_cross_kernel(const int32_t* __restrict__ segid, const int32_t* __restri
     acc[2 * c + 1] = x.y;
   }
   float aw = gw ? partw[run * 2 + 1] : 0.f;
-  if (kB == 1) {  // (one run per iteration, the compiler's unroll)
-#pragma unroll 8
-    for (int64_t r = run + 1; r <= re; ++r) {
+#pragma unroll 8  // (one run per iteration, the compiler's unroll)
+  for (int64_t r = run + 1; r <= re; ++r) {
 #pragma unroll
-      for (int c = 0; c < C; ++c) {
-        const float2 x = *reinterpret_cast<const float2*>(part + r * 2 * D + c * 128 + 2 * lane);
-        acc[2 * c] += x.x;
-        acc[2 * c + 1] += x.y;
-      }
-      if (gw) aw += partw[r * 2];
+    for (int c = 0; c < C; ++c) {
+      const float2 x = *reinterpret_cast<const float2*>(part + r * 2 * D + c * 128 + 2 * lane);
+      acc[2 * c] += x.x;
+      acc[2 * c + 1] += x.y;
     }
-  } else
-  for (int64_t r0 = run + 1; r0 <= re; r0 += kB) {
-    float2 x[kB][C];
-    float xw[kB];
-#pragma unroll
-    for (int q = 0; q < kB; ++q) {
-      const int64_t r = r0 + q <= re ? r0 + q : re;
-#pragma unroll
-      for (int c = 0; c < C; ++c)
-        x[q][c] = *reinterpret_cast<const float2*>(part + r * 2 * D + c * 128 + 2 * lane);
-      xw[q] = gw ? partw[r * 2] : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < kB; ++q) {
-      if (r0 + q > re) break;
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        acc[2 * c] += x[q][c].x;
-        acc[2 * c + 1] += x[q][c].y;
-      }
-      aw += xw[q];
-    }
+    if (gw) aw += partw[r * 2];
   }
 #pragma unroll
   for (int c = 0; c < C; ++c)
@@ -856,14 +829,6 @@ int64_t emb_grad_part_floats(int64_t nnz, int D) {
   return seg_path(D) ? ((nnz + kSegRun - 1) / kSegRun) * 2 * (D + 1) : 0;
 }
 bool emb_grad_wide_ok(int D) { return D == 128 || D == 256; }
-// PSAMD_CROSS_BATCH=1: the cross kernel loads kB runs' partials per iteration (A/B)
-static bool cross_batched() {
-  static const bool on = [] {
-    const char* e = getenv("PSAMD_CROSS_BATCH");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
 
 void emb_grad_reduce(const int32_t* pos_s, const int32_t* segid, const int32_t* seg_start,
                      const int32_t* n_uniq, int64_t u_cap, int64_t nnz, const void* dX0, int D,
@@ -895,22 +860,14 @@ void emb_grad_reduce(const int32_t* pos_s, const int32_t* segid, const int32_t* 
       emb_grad_seg_kernel<1><<<grid, 256, 0, st>>>(pos_s, segid, seg_start, u_cap, nnz, x, dE, part,
                                                     coef, width, gw, partw);
       PSAMD_HIP_CHECK(hipGetLastError());
-      if (cross_batched())
-        emb_grad_cross_kernel<1, 16><<<grid, 256, 0, st>>>(segid, seg_start, u_cap, nnz, part, dE,
-                                                           partw, gw);
-      else
-        emb_grad_cross_kernel<1, 1><<<grid, 256, 0, st>>>(segid, seg_start, u_cap, nnz, part, dE,
-                                                          partw, gw);
+      emb_grad_cross_kernel<1><<<grid, 256, 0, st>>>(segid, seg_start, u_cap, nnz, part, dE, partw,
+                                                     gw);
     } else {
       emb_grad_seg_kernel<2><<<grid, 256, 0, st>>>(pos_s, segid, seg_start, u_cap, nnz, x, dE, part,
                                                     coef, width, gw, partw);
       PSAMD_HIP_CHECK(hipGetLastError());
-      if (cross_batched())
-        emb_grad_cross_kernel<2, 8><<<grid, 256, 0, st>>>(segid, seg_start, u_cap, nnz, part, dE,
-                                                          partw, gw);
-      else
-        emb_grad_cross_kernel<2, 1><<<grid, 256, 0, st>>>(segid, seg_start, u_cap, nnz, part, dE,
-                                                          partw, gw);
+      emb_grad_cross_kernel<2><<<grid, 256, 0, st>>>(segid, seg_start, u_cap, nnz, part, dE, partw,
+                                                     gw);
     }
 #undef PSAMD_NARROW
     PSAMD_HIP_CHECK(hipGetLastError());

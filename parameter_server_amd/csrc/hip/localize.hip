@@ -5,7 +5,7 @@
 // them; remapIndex (:126-191) merge-joins against a key dictionary and emits a
 // CSR with uint32 local column ids. Here:
 //   1. mix:    h = mix(key) (bijection, see common.cuh), pos = iota
-//   2. sort:   rocPRIM/hipCUB LSD radix sort of (h, pos) over only the `bits`
+//   2. sort:   LSD radix sort (primitives.hip) of (h, pos) over only the `bits`
 //              significant bits of the mixed key space (30 bits for 10^9
 //              features => 4 digit passes instead of 8)
 //   3. RLE:    head flags -> inclusive scan -> scatter: unique keys (sorted,
@@ -14,7 +14,6 @@
 //   4. split:  owner boundaries by binary search (K14, sliceKeyOrderedMsg,
 //              src/system/message.h:120-159)
 #include "common.cuh"
-#include <hipcub/hipcub.hpp>
 #include <stdexcept>
 #include <string>
 
@@ -145,22 +144,6 @@ void mix_keys(const uint64_t* keys, int64_t n, KeyMix m, uint64_t* h, bool inver
               hipStream_t st) {
   mix_kernel<<<grid_for(n, 256), 256, 0, st>>>(keys, n, m, h, inverse ? 1 : 0);
   PSAMD_HIP_CHECK(hipGetLastError());
-}
-
-// rocPRIM reference path (kept for A/B benchmarking; not used by the trainer).
-size_t rocprim_sort_temp_bytes(int64_t n, int end_bit) {
-  size_t bytes = 0;
-  PSAMD_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
-      nullptr, bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const int32_t*)nullptr,
-      (int32_t*)nullptr, (int)n, 0, end_bit, (hipStream_t)0));
-  return bytes;
-}
-
-void rocprim_sort_pairs(void* temp, size_t temp_bytes, const uint64_t* k_in, uint64_t* k_out,
-                        const int32_t* v_in, int32_t* v_out, int64_t n, int end_bit,
-                        hipStream_t st) {
-  PSAMD_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, k_in, k_out, v_in, v_out,
-                                                     (int)n, 0, end_bit, st));
 }
 
 size_t scan_i32_temp_bytes(int64_t n);

@@ -2423,253 +2423,6 @@ tpf_step_kernel(int do_upd, const int32_t* __restrict__ cntA, const int32_t* __r
   }
 }
 
-// Overlapped form of tpf_step_kernel (opt-in, PSAMD_TPF_STEP2=1: measured SLOWER, see
-// tpf_step below; the chain-latency model that motivated it did not hold): the dependent global-load chains of
-// the step run together instead of one after another. tpf_step_kernel walks unit 0's
-// update, unit 1's update, unit 0's pull, unit 1's pull, each a chain of dependent
-// loads (entry -> partial; key -> slot record; key -> hash probe) behind barriers: ~12
-// load latencies per workgroup, with ~114 keys and ~500 entries per unit too little
-// work to hide them (19 us per half, profiles/r4_flat_ab.log). Here both units are one
-// flat index space and, before the first barrier, every thread issues its A entries'
-// partial loads, its A keys' slot records and its B keys' hash probes (lookup-or-insert:
-// the slot a key resolves to does not depend on A's update), so the chain is about
-// four latencies: prefetch | LDS fixed-point sums | update + store | re-read of the
-// weights of B keys that existed (A may have updated them) | scatter. The pulled
-// weights reuse the accumulators' LDS. Same results as tpf_step_kernel (same
-// per-unit scales, same fixed-point sums, same per-key update).
-namespace tpf2 {
-constexpr int kRE = 8;   // A entries held in registers per thread (2048 per workgroup)
-constexpr int kRS = 2;   // A slot records held in registers per thread (512 keys)
-constexpr int kRP = 4;   // B probes held in registers per thread (1024 keys)
-constexpr int kRB = 8;   // B entries held in registers per thread
-}  // namespace tpf2
-
-__global__ void __launch_bounds__(tpf::kThr)
-tpf_step2_kernel(int do_upd, const int32_t* __restrict__ cntA, const int32_t* __restrict__ posA,
-                 const uint16_t* __restrict__ jA, const uint32_t* __restrict__ slotA,
-                 const float* __restrict__ psum, int64_t p_cap, int do_res,
-                 const int32_t* __restrict__ cntB, const uint64_t* __restrict__ uniqB,
-                 const int32_t* __restrict__ posB, const uint16_t* __restrict__ jB,
-                 uint32_t* __restrict__ slotB, float* __restrict__ w_ent, int64_t w_cap,
-                 Slot* __restrict__ slots, uint64_t mask, uint64_t home_base, uint64_t home_m,
-                 int home_shr, int init_type, float init_v, float init_s, uint64_t seed,
-                 int32_t* __restrict__ err, int32_t* __restrict__ inserted, UpdateParams p,
-                 double* __restrict__ stats, int acc_stripes, uint32_t* __restrict__ hist,
-                 int nbins, int hist_stripes, double* __restrict__ metrics,
-                 int64_t* __restrict__ step_counter) {
-  using namespace tpf;
-  using namespace tpf2;
-  __shared__ long long acc[2 * kUnitK];  // fixed-point sums of both units; then B weights
-  __shared__ uint32_t smax[2];
-  float* wj = reinterpret_cast<float*>(acc);
-  const int t = threadIdx.x, b = blockIdx.x, lane = t & 63;
-  if (do_upd && hist && b == (int)gridDim.x - 1) {  // (an extra workgroup, as tpf_step_kernel)
-    auc_hist_block(hist, nbins, hist_stripes, metrics, step_counter);
-    return;
-  }
-  // per-unit counts (clamped to the regions: a corrupted count never leaves them)
-  int DA0 = 0, DA1 = 0, EA0 = 0, EA = 0, DB0 = 0, DB1 = 0, EB0 = 0, EB = 0;
-  if (do_upd) {
-    const int32_t* c = cntA + (int64_t)b * 4;
-    EA0 = min(max(c[1], 0), kEC);
-    DA0 = max(min(c[0], kUnitK), 0);
-    DA1 = max(min(c[2], kUnitK), 0);
-    EA = EA0 + max(min(c[3], kEC - EA0), 0);
-  }
-  if (do_res) {
-    const int32_t* c = cntB + (int64_t)b * 4;
-    EB0 = min(max(c[1], 0), kEC);
-    DB0 = max(min(c[0], kUnitK), 0);
-    DB1 = max(min(c[2], kUnitK), 0);
-    EB = EB0 + max(min(c[3], kEC - EB0), 0);
-  }
-  const int DA = DA0 + DA1, DB = DB0 + DB1;
-  const int64_t ebase = (int64_t)b * kEC, kbase = (int64_t)b * kUC;
-  // key q of the flat index space -> its slot in the key region (unit 1 after unit 0)
-  auto kreg = [&](int q, int D0) -> int64_t {
-    return kbase + (q < D0 ? q : kUnitK + (q - D0));
-  };
-  auto kacc = [&](int q, int D0) -> int { return q < D0 ? q : kUnitK + (q - D0); };
-  // ---- prefetch: A entries' partials, A keys' slot records, B keys' probes, B entries
-  float v[kRE];
-  uint16_t ja[kRE];
-  float vmax0 = 0.f, vmax1 = 0.f;
-  // (loads in batches at clamped in-region addresses, selects afterwards: a guarded load
-  // per element compiles to a branch + s_waitcnt each)
-  // (A's arrays are null on a pull-only launch: every A load is under do_upd)
-  uint32_t sa[kRS];
-  Slot sl[kRS];
-#pragma unroll
-  for (int r = 0; r < kRE; ++r) {
-    v[r] = 0.f;
-    ja[r] = 0;
-  }
-#pragma unroll
-  for (int i = 0; i < kRS; ++i) sa[i] = kNoSlot;
-  if (do_upd) {
-    int32_t pa[kRE];
-#pragma unroll
-    for (int r = 0; r < kRE; ++r) {
-      const int g = r * kThr + t;
-      const int64_t gi = ebase + (g < EA ? g : 0);
-      pa[r] = posA[gi];
-      ja[r] = jA[gi];
-    }
-#pragma unroll
-    for (int r = 0; r < kRE; ++r) {
-      const bool ok = r * kThr + t < EA && in_range(pa[r], p_cap);
-      const float x = psum[ok ? pa[r] : 0];
-      v[r] = ok ? x : 0.f;
-      if (r * kThr + t >= EA) ja[r] = 0;
-    }
-#pragma unroll
-    for (int i = 0; i < kRS; ++i) {
-      const int q = i * kThr + t;
-      const uint32_t si = slotA[q < DA ? kreg(q, DA0) : kbase];
-      sa[i] = (q < DA && si != kNoSlot && si <= mask) ? si : kNoSlot;
-    }
-#pragma unroll
-    for (int i = 0; i < kRS; ++i) sl[i] = slots[sa[i] != kNoSlot ? sa[i] : 0];
-  }
-  uint32_t sb[kRP];
-  float wb[kRP];
-  bool fresh[kRP];
-  int ins = 0;
-#pragma unroll
-  for (int i = 0; i < kRP; ++i) {
-    const int q = i * kThr + t;
-    sb[i] = kNoSlot;
-    wb[i] = 0.f;
-    fresh[i] = false;
-    if (q < DB) {
-      const int ins0 = ins;
-      sb[i] = tpf_resolve(slots, mask, home_base, home_m, home_shr, uniqB[kreg(q, DB0)],
-                          init_type, init_v, init_s, seed, &wb[i], &ins);
-      fresh[i] = ins != ins0;  // inserted now: not in A, its weight is final
-      if (sb[i] == kNoSlot && err) atomicOr(err, 1);  // table full
-      slotB[kreg(q, DB0)] = sb[i];
-    }
-  }
-  int32_t pb[kRB];
-  uint16_t jb[kRB];
-#pragma unroll
-  for (int r = 0; r < kRB; ++r) {
-    const int g = r * kThr + t;
-    pb[r] = -1;
-    jb[r] = 0;
-    if (g < EB) {
-      pb[r] = posB[ebase + g];
-      jb[r] = jB[ebase + g];
-    }
-  }
-  double dnnz = 0, wsum = 0, dsum = 0;
-  if (do_upd) {
-    for (int q = t; q < DA; q += kThr) acc[kacc(q, DA0)] = 0ll;
-    if (t < 2) smax[t] = 0u;
-#pragma unroll
-    for (int r = 0; r < kRE; ++r) {
-      const int g = r * kThr + t;
-      if (g < EA0) vmax0 = fmaxf(vmax0, fabsf(v[r]));
-      else vmax1 = fmaxf(vmax1, fabsf(v[r]));
-    }
-    for (int g = kRE * kThr + t; g < EA; g += kThr) {  // (rare: > 2048 entries)
-      const int32_t pos = posA[ebase + g];
-      const float x = in_range(pos, p_cap) ? fabsf(psum[pos]) : 0.f;
-      if (g < EA0) vmax0 = fmaxf(vmax0, x);
-      else vmax1 = fmaxf(vmax1, x);
-    }
-    __syncthreads();  // acc / smax zeroed
-    fx_tile_max(vmax0, &smax[0]);
-    fx_tile_max(vmax1, &smax[1]);
-    __syncthreads();
-    const int k20 = fx_shift(smax[0]), k21 = fx_shift(smax[1]);
-    const double sc0 = ldexp(1.0, k20), sc1 = ldexp(1.0, k21);
-#pragma unroll
-    for (int r = 0; r < kRE; ++r) {
-      const int g = r * kThr + t;
-      if (g < EA && v[r] != 0.f && ja[r] < kUnitK) {
-        const bool u1 = g >= EA0;
-        fx_add(acc, (u1 ? kUnitK : 0) + ja[r], v[r], u1 ? sc1 : sc0);
-      }
-    }
-    for (int g = kRE * kThr + t; g < EA; g += kThr) {
-      const int32_t pos = posA[ebase + g];
-      const uint16_t j = jA[ebase + g];
-      const float x = in_range(pos, p_cap) ? psum[pos] : 0.f;
-      const bool u1 = g >= EA0;
-      if (x != 0.f && j < kUnitK) fx_add(acc, (u1 ? kUnitK : 0) + j, x, u1 ? sc1 : sc0);
-    }
-    __syncthreads();
-    const double isc0 = ldexp(1.0, -k20), isc1 = ldexp(1.0, -k21);
-    auto upd = [&](int q, Slot& s_, uint32_t si) {
-      const double isc = q < DA0 ? isc0 : isc1;
-      const float gs = (float)((double)acc[kacc(q, DA0)] * isc) * p.grad_scale;
-      if (gs != gs) return;
-      const float w_old = apply_update(s_, gs, p);
-      slots[si] = s_;
-      dnnz += (double)((s_.w != 0.f) - (w_old != 0.f));
-      wsum += (double)s_.w * s_.w;
-      const double d = (double)s_.w - w_old;
-      dsum += d * d;
-    };
-#pragma unroll
-    for (int i = 0; i < kRS; ++i)
-      if (sa[i] != kNoSlot) upd(i * kThr + t, sl[i], sa[i]);
-    for (int q = kRS * kThr + t; q < DA; q += kThr) {  // (rare: > 512 keys)
-      const uint32_t si = slotA[kreg(q, DA0)];
-      if (si == kNoSlot || si > mask) continue;
-      Slot s_ = slots[si];
-      upd(q, s_, si);
-    }
-    __syncthreads();  // (the updated records are what B re-reads; acc is free for wj)
-  }
-  if (do_res) {
-#pragma unroll
-    for (int i = 0; i < kRP; ++i) {
-      const int q = i * kThr + t;
-      if (q >= DB) continue;
-      float w = wb[i];
-      // a key that existed may have been updated by A just now: its weight again
-      if (do_upd && !fresh[i] && sb[i] != kNoSlot) w = slots[sb[i]].w;
-      wj[kacc(q, DB0)] = w;
-    }
-    for (int q = kRP * kThr + t; q < DB; q += kThr) {  // (rare: > 1024 keys)
-      float w;
-      const uint32_t si = tpf_resolve(slots, mask, home_base, home_m, home_shr,
-                                      uniqB[kreg(q, DB0)], init_type, init_v, init_s, seed, &w,
-                                      &ins);
-      if (si == kNoSlot && err) atomicOr(err, 1);
-      slotB[kreg(q, DB0)] = si;
-      wj[kacc(q, DB0)] = w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < kRB; ++r) {
-      const int g = r * kThr + t;
-      if (g < EB && in_range(pb[r], w_cap) && jb[r] < kUnitK)
-        w_ent[pb[r]] = wj[(g >= EB0 ? kUnitK : 0) + jb[r]];
-    }
-    for (int g = kRB * kThr + t; g < EB; g += kThr) {
-      const int32_t pos = posB[ebase + g];
-      const uint16_t j = jB[ebase + g];
-      if (in_range(pos, w_cap) && j < kUnitK) w_ent[pos] = wj[(g >= EB0 ? kUnitK : 0) + j];
-    }
-  }
-  if (do_upd && stats) {
-    const double a = wave_sum_dpp(dnnz), bb = wave_sum_dpp(wsum), cc = wave_sum_dpp(dsum);
-    if (lane == 63) {
-      double* st = acc_stripe(stats, acc_stripes);
-      if (a != 0) atomicAdd(&st[0], a);
-      if (bb != 0) atomicAdd(&st[1], bb);
-      if (cc != 0) atomicAdd(&st[2], cc);
-    }
-  }
-  if (inserted) {
-    const int tot = wave_sum(ins);
-    if (lane == 0 && tot) atomicAdd(inserted, tot);
-  }
-}
-
 // ---- the padded multi-GPU exchange on the flat layout (G peers, G a power of two that
 // divides the bucket workgroups: owner p's key range is exactly the buckets
 // [p * B / G, (p + 1) * B / G), whose keys are rank-sorted (tpf_bucket sorted = 1), so
@@ -2697,72 +2450,27 @@ __device__ __forceinline__ uint64_t tpf_key_at(const uint64_t* __restrict__ uniq
                 : uniqf[(int64_t)b * tpf::kUC + tpf::kUnitK + (i - D0)];
 }
 
-// homes != null (the merged exchange): the row also carries, at word b0, the bounds of
-// the owner's 2^lgP key-range partitions over the row's sorted keys (bnd[q] = # keys of
-// partitions < q, bnd[P] = row count) -- what the owner's one-launch resolve + apply
-// (kv_owner_part) needs to find its partition's run in every row. homes[2p], [2p+1] =
-// owner p's ordered-home (base, m) (kv_slot.cuh key_part).
 __global__ void __launch_bounds__(tpf::kThr)
 tpf_pack_keys_kernel(const int32_t* __restrict__ cnt, const uint64_t* __restrict__ uniqf, int per,
                      int64_t C, int kw, int64_t H, int32_t* __restrict__ send,
-                     int32_t* __restrict__ ovf, const uint64_t* __restrict__ homes, int64_t b0,
-                     int lgP) {
+                     int32_t* __restrict__ ovf) {
   using namespace tpf;
   __shared__ uint32_t red[kThr / 64 + 1];
   const int b = blockIdx.x, p = b / per, t = threadIdx.x;
   const int base = tpf_row_base(cnt, b, per, red);
   const int D0 = min(cnt[4 * b], kUnitK), D1 = min(cnt[4 * b + 2], kUnitK);
   int32_t* row = send + (int64_t)p * H;
-  const int P = 1 << lgP;
-  const uint64_t hb = homes ? homes[2 * p] : 0, hm = homes ? homes[2 * p + 1] : 0;
-  int32_t* rb = row + b0;
-  // the key before this bucket's first one in the row: the last key of the nearest
-  // non-empty earlier bucket of the same owner (none: the row's first key)
-  int qprev = -1;
-  if (homes && base > 0 && t == 0) {
-    for (int c = b - 1; c >= (b / per) * per; --c) {
-      const int e0 = min(cnt[4 * c], kUnitK), e1 = min(cnt[4 * c + 2], kUnitK);
-      if (e0 + e1 > 0) {
-        qprev = key_part(tpf_key_at(uniqf, c, e0, e0 + e1 - 1), hb, hm, lgP);
-        break;
-      }
-    }
-  }
-  if (homes) {  // (broadcast qprev through the scan scratch)
-    __syncthreads();
-    if (t == 0) red[0] = (uint32_t)(qprev + 1);
-    __syncthreads();
-    qprev = (int)red[0] - 1;
-  }
   for (int i = t; i < D0 + D1; i += kThr) {
     const int64_t pos = (int64_t)base + i;
     if (pos >= C) break;
     const uint64_t k = tpf_key_at(uniqf, b, D0, i);
     if (kw == 1) row[4 + pos] = (int32_t)(uint32_t)k;
     else reinterpret_cast<uint64_t*>(row + 4)[pos] = k;
-    if (homes) {
-      const int q = key_part(k, hb, hm, lgP);
-      const int q0 = (i > 0 ? key_part(tpf_key_at(uniqf, b, D0, i - 1), hb, hm, lgP) : qprev) + 1;
-      for (int j = q0; j <= q; ++j) rb[j] = (int32_t)pos;
-      if (pos == C - 1)  // a full row ends here
-        for (int j = q + 1; j <= P; ++j) rb[j] = (int32_t)C;
-    }
   }
   if (t == 0 && b % per == per - 1) {
     const int64_t tot = (int64_t)base + D0 + D1;
     row[0] = (int32_t)(tot < C ? tot : C);
     if (tot > C && ovf) atomicAdd(ovf, (int32_t)(tot - C));
-    if (homes && tot <= C) {  // the row's tail bounds after its last key
-      int qlast = -1;
-      for (int c = b; c >= (b / per) * per; --c) {
-        const int e0 = min(cnt[4 * c], kUnitK), e1 = min(cnt[4 * c + 2], kUnitK);
-        if (e0 + e1 > 0) {
-          qlast = key_part(tpf_key_at(uniqf, c, e0, e0 + e1 - 1), hb, hm, lgP);
-          break;
-        }
-      }
-      for (int j = qlast + 1; j <= P; ++j) rb[j] = (int32_t)tot;
-    }
   }
 }
 
@@ -3035,8 +2743,7 @@ void localize_tp(const uint64_t* raw, int64_t n, KeyMix m, void* temp, size_t te
   uint32_t* epoch = (uint32_t*)(status + g.nbk);
   uint32_t* tkeys = (uint32_t*)take((size_t)g.N * 4);
   uint16_t* toff = (uint16_t*)take((size_t)g.T * (g.nbk + 1) * 2);
-  static const char* quot_env = getenv("PSAMD_TP_QUOT");  // "1": A/B the encoding at <= 31 bits
-  if (m.bits > 31 || (quot_env && quot_env[0] == '1'))
+  if (m.bits > 31)
     tp_tile_kernel<true><<<(unsigned)g.T, tp::kThr, 0, st>>>(raw, n, m, g.shift, g.nbk, tkeys, toff,
                                                              dcnt, rep, err, g.lts);
   else
@@ -3057,14 +2764,7 @@ void localize_tp(const uint64_t* raw, int64_t n, KeyMix m, void* temp, size_t te
 }
 
 // ---- flat (tpf) host side
-// (PSAMD_TPF_PAIR=0: one fine bucket per workgroup -- measurement of the pair layout)
-static bool tpf_pair(const TpGeom& g) {
-  static const int force = [] {
-    const char* e = std::getenv("PSAMD_TPF_PAIR");
-    return e ? std::atoi(e) : -1;
-  }();
-  return g.nbk >= 2 && g.shift <= 30 && force != 0;
-}
+static bool tpf_pair(const TpGeom& g) { return g.nbk >= 2 && g.shift <= 30; }
 static int tpf_groups_of(const TpGeom& g) { return tpf_pair(g) ? g.nbk / 2 : g.nbk; }
 int tpf_groups(int64_t n, int bits) { return tpf_groups_of(tp_geom(n, bits)); }
 int tpf_key_region() { return tpf::kUC; }
@@ -3146,11 +2846,10 @@ static int tpf_per_owner(int64_t n, int bits, int G) {
 }
 
 void tpf_pack_keys(int64_t n, int bits, int G, const int32_t* cnt, const uint64_t* uniqf, int64_t C,
-                   int kw, int64_t H, int32_t* send, int32_t* ovf, const uint64_t* homes,
-                   int64_t b0, int lgP, hipStream_t st) {
+                   int kw, int64_t H, int32_t* send, int32_t* ovf, hipStream_t st) {
   const int per = tpf_per_owner(n, bits, G);
   tpf_pack_keys_kernel<<<(unsigned)tpf_groups(n, bits), tpf::kThr, 0, st>>>(
-      cnt, uniqf, per, C, kw, H, send, ovf, homes, b0, lgP);
+      cnt, uniqf, per, C, kw, H, send, ovf);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
@@ -3196,21 +2895,11 @@ void tpf_step(int64_t n, int bits, const int32_t* cntA, const int32_t* posA, con
   while ((1ll << lg) < cap) ++lg;
   UpdateParams p{algo, lr_type, alpha, beta, l1, l2, grad_scale, max_delta};
   const int groups = tpf_groups(n, bits);
-  // PSAMD_TPF_STEP2=1: the overlapped form (measured slower: 28.7-30.2 vs 24.9-25.4 us per
-  // update + pull launch, profiles/r4_tpf_step_probe.log; kept for A/B and its test)
-  const char* v2_env = getenv("PSAMD_TPF_STEP2");
-  if (!(v2_env && v2_env[0] == '1'))
-    tpf_step_kernel<<<(unsigned)groups + (cntA && hist ? 1u : 0u), tpf::kThr, 0, st>>>(
-        cntA != nullptr, cntA, posA, jA, slotA, psum, p_cap, cntB != nullptr, cntB, uniqB, posB,
-        jB, slotB, w_ent, w_cap, (Slot*)slots, (uint64_t)(cap - 1), home_base, home_m, 64 - lg,
-        init_type, init_v, init_s, seed, err, inserted, p, stats, acc_stripes,
-        cntA ? hist : nullptr, nbins, hist_stripes, metrics, step_counter);
-  else
-    tpf_step2_kernel<<<(unsigned)groups + (cntA && hist ? 1u : 0u), tpf::kThr, 0, st>>>(
-        cntA != nullptr, cntA, posA, jA, slotA, psum, p_cap, cntB != nullptr, cntB, uniqB, posB,
-        jB, slotB, w_ent, w_cap, (Slot*)slots, (uint64_t)(cap - 1), home_base, home_m, 64 - lg,
-        init_type, init_v, init_s, seed, err, inserted, p, stats, acc_stripes,
-        cntA ? hist : nullptr, nbins, hist_stripes, metrics, step_counter);
+  tpf_step_kernel<<<(unsigned)groups + (cntA && hist ? 1u : 0u), tpf::kThr, 0, st>>>(
+      cntA != nullptr, cntA, posA, jA, slotA, psum, p_cap, cntB != nullptr, cntB, uniqB, posB,
+      jB, slotB, w_ent, w_cap, (Slot*)slots, (uint64_t)(cap - 1), home_base, home_m, 64 - lg,
+      init_type, init_v, init_s, seed, err, inserted, p, stats, acc_stripes,
+      cntA ? hist : nullptr, nbins, hist_stripes, metrics, step_counter);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
@@ -3220,9 +2909,7 @@ void tp_backward(const uint16_t* rep, const int32_t* dcnt, int64_t n, const int3
                  int64_t grad_cap, hipStream_t st) {
   if (n <= 0) return;
   const TpGeom g = tp_geom(n, 31);
-  static const char* bwd_env = getenv("PSAMD_TP_BWD");  // "rows": A/B the row-major walk
-  const bool cols = !(bwd_env && bwd_env[0] == 'r');
-  if (cols && rows == nullptr && width >= 2 && width <= tp::kThr)
+  if (rows == nullptr && width >= 2 && width <= tp::kThr)
     tp_bwd_accum_cols_kernel<<<(unsigned)g.T, tp::kThr, 0, st>>>(rep, dcnt, n, width, vals, coef,
                                                                  B, psum);
   else

@@ -115,15 +115,10 @@ class DarlinConfig:
 _SMALL_ROWS_BLOCK = 1 << 18
 
 
-_FUSED_W = int(os.environ.get("PSAMD_BCD_FUSED_W", "0"))  # (A/B pin of the fused grid)
-
-
 def _hot_piece(entries: int) -> int:
     """Entries per piece of a hot column in the chunked gradient: ~2048 pieces per block
     (256 .. 4096), so a block of a few 100 k entries is not a few dozen waves each
     walking 4096 dependent gathers (CTR-log groups: 44.7 us per wide block at 4096)."""
-    if os.environ.get("PSAMD_BCD_HOT"):  # (A/B pin)
-        return int(os.environ["PSAMD_BCD_HOT"])
     want = max(1, entries // 2048)
     return int(min(4096, max(256, 1 << (want - 1).bit_length())))
 
@@ -516,14 +511,14 @@ class DarlinTrainer:
         self.fuse_rows = dev.type == "cuda" and os.environ.get("PSAMD_DARLIN_FUSE", "1") != "0"
         self._pending_dual = None
         # workgroups of the row-order gradient and row pass and their partial-sum buffer
-        self.rows_W = int(os.environ.get("PSAMD_BCD_W", "256"))
+        self.rows_W = 256
         rows_max = hipops().bcd_rows_max_cols() if dev.type == "cuda" else 0
         # (+ the row pass's segment sums behind the partials; hot-column passes of wide
         # blocks use fewer workgroups, rows_W_hot: their per-workgroup setup and partials
         # cover 2048 columns)
         # (256 = one workgroup per CU for both: 2.84 ms / pass vs 3.10 at 768 narrow,
         # 3.06 / 3.36 at 192 / 320 hot; profiles/r3_darlin_rowpass.log)
-        self.rows_W_hot = int(os.environ.get("PSAMD_BCD_WHOT", "256"))
+        self.rows_W_hot = 256
         nseg = hipops().bcd_part_segments() if dev.type == "cuda" else 0
         self.rows_part = (torch.empty((max(self.rows_W, self.rows_W_hot) + nseg) * 2 *
                                       max(rows_max, 1),
@@ -681,7 +676,7 @@ class DarlinTrainer:
             c = self.cfg
             # (8 workgroups for a ~60 k-entry block: 17.3 ms per pass vs 18.1 at 4, 18.2 at
             # ~15, 18.1 at 32, 20.6 at 64; profiles/r5_darlin_groups.log)
-            W = _FUSED_W or max(8, min(32, (b.p1 - b.p0) // 8192))
+            W = max(8, min(32, (b.p1 - b.p0) // 8192))
             bcd.grad_rows(self.col_r, self.row_r, self.val_r, b.p0, b.p1, b.c0, b.ncols, self.ym,
                           self.y, self.delta, self.active, G, U, b.part2, W, b.fx_k,
                           upd=dict(w=self.w, dw=b.dw, vio=self.vio, counter=self._upd_ctr,

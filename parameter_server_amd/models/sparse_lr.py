@@ -176,7 +176,6 @@ class SparseLRTrainer:
         # 1 GPU: entry scan + optimizer update fused (PSAMD_FUSED_UPDATE=0: scan, then
         # kv_update); read once, not per step (host issue time)
         self._fused_update = os.environ.get("PSAMD_FUSED_UPDATE", "1") != "0"
-        self._use_plans = os.environ.get("PSAMD_STEP_PLAN", "1") != "0"
         mode = cfg.localize
         # the flat layout (Localizer "tpf": fixed per-bucket regions, ops/localize.FlatLoc):
         # 1 GPU: the step's pull fused into the previous step's update (tpf_step); G > 1
@@ -186,7 +185,7 @@ class SparseLRTrainer:
         self._flat_x = False  # G > 1: the padded exchange on the flat layout
         # (the tail filter runs inside the flat bucket kernel: tpf_filter_unit)
         if self.G == 1:
-            flat_ok = self.gpu and self._fused_update and self._use_plans and flat_env
+            flat_ok = self.gpu and self._fused_update and flat_env
         else:
             flat_ok = self._flat_x = bool(
                 self.gpu and flat_env and cfg.exchange == "padded"
@@ -383,7 +382,7 @@ class SparseLRTrainer:
         if width is None and row_ptr is None:
             width = self.cfg.max_nnz_per_example
         if (self.G == 1 and self.gpu and self.filter is None and self._fused_update
-                and self._use_plans and row_ptr is None and rows is None and vals is None and prefetch is None
+                and row_ptr is None and rows is None and vals is None and prefetch is None
                 and not trace_enabled()):
             if loc is None:
                 loc = self.localizer(keys)
@@ -879,21 +878,6 @@ class SparseLRTrainer:
             if s - d >= 0:
                 self._x_apply(b, (s - d) % R)
 
-        if xc.fused:  # resolve + apply of the owner in ONE launch (kv_owner_part)
-            def owner():
-                tb, ra = self.table, (s - d) % R
-                it, iv, isd, seed = tb.init.args()
-                gsrc, gstride = self._x_grads(b) if s - d >= 0 else (None, 0)
-                ap = s - d >= 0
-                hipops().kv_owner_part(
-                    tb.slots, recv, xc.H, xc.C, xc.kw, xc.b0, xc.lgP, xc.slots[bn],
-                    xc.pkeys[bn], xc.bnd[bn], self._mx_wview(xc.sends[bn]), it, iv, isd, seed,
-                    tb._err, tb._inserted, tb.home_base, tb.home_m,
-                    xc.slots[ra] if ap else None, xc.pkeys[ra] if ap else None, gsrc, gstride,
-                    xc.bnd[ra] if ap else None, ms.post, *self.rule.args(), self.stats)
-
-            return {"pack": pack, "comm": lambda: comm.all_to_all_fixed(send, recv),
-                    "resolve": owner, "apply": lambda: None, "post": ms.post}
         return {"pack": pack, "comm": lambda: comm.all_to_all_fixed(send, recv),
                 "resolve": resolve, "apply": apply, "post": ms.post}
 
@@ -1140,31 +1124,23 @@ class SparseLRTrainer:
         gw = (C * nb + 3) // 4 if nb else C
         # the partitioned apply needs rows sorted by key and an ordered home (key range
         # -> partition)
-        part_apply = (self.gpu and cfg.push_mode != "aggregate" and self.table.home_m != 0
-                      and os.environ.get("PSAMD_OWNER_APPLY", "part") == "part")
+        part_apply = self.gpu and cfg.push_mode != "aggregate" and self.table.home_m != 0
         # ~G*C/512 partitions (~1-2 entries per thread of a 256-thread workgroup, rows
         # are ~2/3 full): a few workgroups per CU hide the chain of dependent loads each
         # one runs; many more (tiny ones) pay per-workgroup setup and stats atomics
         # (profiles/r2_owner_apply.log: 8 x 45120 entries, 2^9 -> 21 us, link pair 58 us)
         lgP = max(0, min(16, math.floor(math.log2(max(1, G * C // 512))))) if part_apply else -1
-        if part_apply and os.environ.get("PSAMD_APPLY_LGP"):
-            lgP = int(os.environ["PSAMD_APPLY_LGP"])
         # merged exchange: each row also carries the owner's weights answering the keys
-        # the row's receiver sent in the previous exchange (word w0) and, for the owner's
-        # one-launch resolve + apply (kv_owner_part), the bounds of its 2^lgP key-range
-        # partitions over the row's keys (word b0, written by the sender's key pack)
-        # (off by default: one launch of both halves measured the SUM of their kernel
-        # times, 56.4 vs 22.3 + 34.4 us at 8 emulated peers, and it puts the apply on the
-        # path to the next collective: 0.175 vs 0.155 ms / step, profiles/r5_owner_fused.log)
-        fused = (self.merged and lgP >= 0
-                 and os.environ.get("PSAMD_OWNER_FUSED", "0") == "1")
+        # the row's receiver sent in the previous exchange (word w0). The owner resolves
+        # and applies in two launches: one launch of both halves measured the SUM of their
+        # kernel times, 56.4 vs 22.3 + 34.4 us at 8 emulated peers, and it puts the apply
+        # on the path to the next collective: 0.175 vs 0.155 ms / step,
+        # profiles/r5_owner_fused.log
         w0 = 4 + C * kw + gw
-        b0 = w0 + (C if self.merged else 0)
-        H = (b0 + (((1 << lgP) + 1) if fused else 0) + 3) // 4 * 4
+        H = (w0 + (C if self.merged else 0) + 3) // 4 * 4
         z32 = lambda n, dt: torch.zeros(n, dtype=dt, device=dev)  # noqa: E731
         self.xc = SimpleNamespace(
-            C=C, kw=kw, H=H, nb=nb, w0=w0, b0=b0, fused=fused,
-            homes=self._owner_homes() if fused else None,
+            C=C, kw=kw, H=H, nb=nb, w0=w0,
             # (+ the flat pack's per-workgroup min / max partials: 2 per bucket group)
             gstage=z32(G * C + 2 * 2048, torch.float32) if nb else None,
             gins=[z32(G * C, torch.float32) for _ in range(R)] if nb else None,
@@ -1190,22 +1166,6 @@ class SparseLRTrainer:
             bnd=([torch.zeros(G * ((1 << lgP) + 1), dtype=torch.int32, device=dev)
                   for _ in range(R)] if lgP >= 0 else None),
             ovf_host=(torch.zeros(1, dtype=torch.int32, pin_memory=True) if self.gpu else None))
-
-    def _owner_homes(self) -> torch.Tensor:
-        """[G, 2] (base, m) of every owner's ordered home (KVTable key_range): the sender
-        computes the owner's key-range partitions of its rows with them (the loopback
-        emulation's one table owns every row)."""
-        M = (1 << 64) - 1
-        if self._loopback:
-            hs = [(self.table.home_base, self.table.home_m)] * self.G
-        else:
-            hs = []
-            for p in range(self.G):
-                lo, hi = self.part.range_of(p)
-                hs.append((lo, M // (hi - lo)) if hi > lo else (0, 0))
-        s64 = lambda x: x - (1 << 64) if x >= (1 << 63) else x  # noqa: E731
-        return torch.tensor([[s64(int(b)), s64(int(m))] for b, m in hs], dtype=torch.int64,
-                            device=self.device)
 
     def _tail_filter(self, loc, ring: int):
         """Tail-feature filter on the padded exchange (reference MinibatchReader::read,
@@ -1276,8 +1236,7 @@ class SparseLRTrainer:
         send = xc.sends[gb]
         if self.gpu:
             hh = hipops()
-            hh.xchg_pack_keys(ukeys, nkeys, off, xc.C, xc.kw, xc.H, send, xc.ovf,
-                              homes=xc.homes, b0=xc.b0, lgP=max(xc.lgP, 0))
+            hh.xchg_pack_keys(ukeys, nkeys, off, xc.C, xc.kw, xc.H, send, xc.ovf)
             if xc.nb:  # (FixingFloat push: no pack_grads launch to carry the flag)
                 hh.xchg_publish(xc.ovf, xc.ovf_host)
             return
@@ -1297,7 +1256,7 @@ class SparseLRTrainer:
         xc.curs[r] = None
         hh = hipops()
         hh.tpf_pack_keys(loc.nnz, loc.bits, self.G, loc.cnt, loc.uniqf, xc.C, xc.kw, xc.H,
-                         xc.sends[gb], xc.ovf, homes=xc.homes, b0=xc.b0, lgP=max(xc.lgP, 0))
+                         xc.sends[gb], xc.ovf)
         # (the overflow flag reaches the host through tpf_pack_grads' extra workgroup,
         # fixing-float or not)
 
@@ -1574,7 +1533,7 @@ class SparseLRTrainer:
         H = (4 + C * kw + gw + 3) // 4 * 4
         i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)  # noqa: E731
         self.xc = SimpleNamespace(
-            C=C, kw=kw, H=H, nb=nb, w0=None, b0=None, fused=False, homes=None, off=off,
+            C=C, kw=kw, H=H, nb=nb, w0=None, off=off,
             send=i32(G * H),
             gstage=torch.zeros(G * C, dtype=torch.float32, device=dev) if nb else None,
             wout=torch.zeros(G * C, dtype=torch.float32, device=dev),

@@ -235,11 +235,8 @@ class Localizer:
             self.hess = torch.empty(n, dtype=torch.float32, device=dev) if with_hess else None
             self.fast32 = self.bits <= 32
             # digit width of the u32 radix sort: 10-bit digits sort 21..30-bit keys in 3
-            # passes (vs 4 with 8 bits); PSAMD_SORT_DIGIT_BITS overrides for A/B runs
-            import os
-
-            db = int(os.environ.get("PSAMD_SORT_DIGIT_BITS", "0"))
-            self.digit_bits = db if db in (8, 10) else (10 if 24 < self.bits <= 30 else 8)
+            # passes (vs 4 with 8 bits)
+            self.digit_bits = 10 if 24 < self.bits <= 30 else 8
             if self.fast32:  # fused mix + u32 radix sort + fused RLE (csrc/hip/sort32.hip)
                 self.hs32 = torch.empty(n, dtype=torch.int32, device=dev)
                 self.sort_temp = torch.empty(H.localize32_temp_bytes(n), dtype=torch.uint8,
@@ -250,8 +247,7 @@ class Localizer:
             # 33..40-bit keys (10^10 features), < 2^22 keys: 4 x 10-bit u32 passes with the
             # high key bits carried next to the position (sort32.hip sort40) instead of
             # the generic 5 x 8-bit u64 sort (65,536 x 39 keys at 34 bits: 420 -> 257 us)
-            self.fast40 = 32 < self.bits <= 40 and n < (1 << 22) and \
-                os.environ.get("PSAMD_SORT40", "1") != "0"
+            self.fast40 = 32 < self.bits <= 40 and n < (1 << 22)
             if self.fast40:
                 self.sort40_temp = torch.empty(H.sort40_temp_bytes(n), dtype=torch.uint8,
                                                device=dev)
