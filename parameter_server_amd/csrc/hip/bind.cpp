@@ -66,6 +66,7 @@ void tp_seg_update(const int32_t*, const int32_t*, int64_t, const int32_t*, cons
 int tpf_groups(int64_t, int);
 int tpf_key_region();
 int tpf_entry_region();
+int tpf_xcd_group(int, int);
 size_t tpf_temp_bytes(int64_t, int);
 void localize_tpf(const uint64_t*, int64_t, KeyMix, void*, size_t, int32_t*, uint16_t*, uint64_t*,
                   int32_t*, uint16_t*, int32_t*, int32_t*, bool, hipStream_t, const CmArgs*,
@@ -1037,6 +1038,11 @@ PYBIND11_MODULE(_hipops, m) {
   m.def("tpf_groups", [](int64_t n, int bits) { return psamd::tpf_groups(n, bits); });
   m.def("tpf_key_region", []() { return psamd::tpf_key_region(); });
   m.def("tpf_entry_region", []() { return psamd::tpf_entry_region(); });
+  // the logical bucket group of physical block bid (tploc.hip tpf_xcd_group_of), host side
+  m.def("tpf_xcd_group", [](int bid, int groups) {
+    check(groups >= 1 && bid >= 0 && bid < groups, "tpf_xcd_group: 0 <= bid < groups");
+    return psamd::tpf_xcd_group(bid, groups);
+  });
   m.def("tpf_temp_bytes", [](int64_t n, int bits) { return psamd::tpf_temp_bytes(n, bits); });
   m.def("localize_tpf", [](Tensor keys, int bits, Tensor temp, Tensor dcnt, Tensor rep,
                            Tensor uniqf, Tensor ent_pos, Tensor ent_j, Tensor cnt, Tensor err,

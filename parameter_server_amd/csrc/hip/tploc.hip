@@ -1587,6 +1587,41 @@ constexpr int kThr = 256;        // tpf_step workgroup (auc_hist_block: an extra
 constexpr uint32_t kNoSlot = 0xffffffffu;
 }  // namespace tpf
 
+// Physical block index -> logical bucket group of the flat bucket-geometry kernels.
+// Entries are laid out per tile (tkeys / psum / w_ent / ecnt[tile * 8192 + position],
+// position = the tile's counting-sort order by fine bucket), so a group's run inside one
+// tile is a few entries and one 128-B line of those arrays (and of a tile's toff row)
+// holds the runs of ~10 (32) neighbouring groups. Blocks are dealt round-robin over the 8
+// XCDs, each with a private L2: with b = blockIdx.x neighbouring groups sit on 8 different
+// XCDs and every such line is fetched into (or partially written from) all 8 L2s. This
+// bijective remap (the form of gemm.hip xcd_swizzle) gives the blocks of one XCD
+// (bid % 8) a contiguous range of groups. The identity for groups < 8. `groups` is the
+// bucket groups, never gridDim.x: tpf_step / tpf_pack_grads launch one extra block (AUC /
+// overflow), which stays the last physical block and is not remapped. Every kernel that
+// uses it is a pure function of its group (no group waits for another); acc_stripe, the
+// hist stripes and the prof slots only spread contention and stay on blockIdx.x.
+// Used by tpf_step_kernel, tpf_unpack_w_kernel and tpf_pack_grads_kernel (device-only,
+// 65,536 x 39, 1024 groups, benchmarks/micro/tpf_xcd_probe.py: step 23.6 -> 18.3 us with
+// L2 fabric reads 802 k -> 593 k and writes 702 k -> 400 k per launch, unpack_w 8.8 -> 5.6,
+// pack_grads 8.9 -> 6.6; profiles/xcd_remap.log). Measured and not kept (a kernel keeps
+// the map only where its own probe time improves by more than its repeats' spread):
+//   tpf_bucket_kernel   fabric reads 320 k -> 47 k per launch, but 16.3 -> 16.4-16.6 us
+//                       (bound by its LDS build, not by these misses); with it mapped too
+//                       the 300-step headline read 0.0743-0.0751 vs 0.0752-0.0754 ms
+//   tpf_filter_kernel   17.4-18.8 min / 34.9-37.0 median vs 18.0-18.3 / 36.1-37.9 us in
+//                       the tail-filtered pipeline: no difference
+//   tpf_pack_keys_kernel  3.24 vs 3.20 us: it reads its keys contiguously per group
+// NOT for tp_bucket_kernel (compact layout): its decoupled look-back relies on dispatch
+// in blockIdx order (a bucket only waits for buckets that are running or done); remapped,
+// a block could spin on one that is not yet resident. Not for the tile-partitioned kernels
+// either (tp_tile, tp_fwd_bwd*): their blocks share no lines.
+__host__ __device__ __forceinline__ int tpf_xcd_group_of(int bid, int groups) {
+  if (groups < 8) return bid;
+  const int q = groups >> 3, r = groups & 7, xcd = bid & 7;
+  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+  return base + (bid >> 3);
+}
+
 // Overflow unit (an overflowing pair's fine bucket f, or a lone bucket whose entries
 // exceed the LDS capacity): register-light like tp_bk_fine_light; entries are located
 // again from the per-tile runs for every pass, their key index found by probing the hash.
@@ -2095,7 +2130,7 @@ tpf_bucket_kernel(const uint32_t* __restrict__ tkeys, const uint16_t* __restrict
   __shared__ uint32_t flag;
   uint32_t* hkey = reinterpret_cast<uint32_t*>(hs);
   uint32_t* hcnt = hkey + kDH;
-  const int t = threadIdx.x, b = blockIdx.x;
+  const int t = threadIdx.x, b = blockIdx.x;  // (tpf_xcd_group_of: measured and not kept)
   const int f0 = pair ? 2 * b : b;
   const uint64_t key0 = (uint64_t)f0 << shift;
   uint64_t* uo = uniqf + (int64_t)b * tpf::kUC;
@@ -2182,7 +2217,7 @@ tpf_filter_kernel(uint64_t* __restrict__ uniqf, int32_t* __restrict__ ent_pos,
   __shared__ uint32_t occs[kFlD];       // occ_small
   __shared__ uint32_t lds[kBkThr / 64 + 3];
   static_assert(kFlTab * 4 <= kDH * 8, "filter LDS");
-  const int t = threadIdx.x, b = blockIdx.x;
+  const int t = threadIdx.x, b = blockIdx.x;  // (tpf_xcd_group_of: measured and not kept)
   uint64_t* uo = uniqf + (int64_t)b * tpf::kUC;
   int32_t* po = ent_pos + (int64_t)b * tpf::kEC;
   uint16_t* jo = ent_j + (int64_t)b * tpf::kEC;
@@ -2284,18 +2319,19 @@ tpf_step_kernel(int do_upd, const int32_t* __restrict__ cntA, const int32_t* __r
                 int32_t* __restrict__ err, int32_t* __restrict__ inserted, UpdateParams p,
                 double* __restrict__ stats, int acc_stripes, uint32_t* __restrict__ hist,
                 int nbins, int hist_stripes, double* __restrict__ metrics,
-                int64_t* __restrict__ step_counter) {
+                int64_t* __restrict__ step_counter, int groups) {
   using namespace tpf;
   __shared__ long long acc[kUnitK];  // fixed-point gradient sums of a unit's keys
   __shared__ float wj[kUnitK];       // pulled weights of a unit's keys
   __shared__ uint32_t smax;
-  const int t = threadIdx.x, b = blockIdx.x, lane = t & 63;
+  const int t = threadIdx.x, lane = t & 63;
   // the step's AUC epilogue in an extra last workgroup of its own (tpf_step launches
   // groups + 1): in unit 0's workgroup its 8 dependent stripe loads delayed that unit
-  if (do_upd && hist && b == (int)gridDim.x - 1) {
-    auc_hist_block(hist, nbins, hist_stripes, metrics, step_counter);
+  if ((int)blockIdx.x >= groups) {
+    if (do_upd && hist) auc_hist_block(hist, nbins, hist_stripes, metrics, step_counter);
     return;
   }
+  const int b = tpf_xcd_group_of(blockIdx.x, groups);
   double dnnz = 0, wsum = 0, dsum = 0;
   if (do_upd) {
     const int32_t* c = cntA + (int64_t)b * 4;
@@ -2456,6 +2492,7 @@ tpf_pack_keys_kernel(const int32_t* __restrict__ cnt, const uint64_t* __restrict
                      int32_t* __restrict__ ovf) {
   using namespace tpf;
   __shared__ uint32_t red[kThr / 64 + 1];
+  // (tpf_xcd_group_of: measured and not kept -- the keys are read contiguously per group)
   const int b = blockIdx.x, p = b / per, t = threadIdx.x;
   const int base = tpf_row_base(cnt, b, per, red);
   const int D0 = min(cnt[4 * b], kUnitK), D1 = min(cnt[4 * b + 2], kUnitK);
@@ -2480,11 +2517,11 @@ __global__ void __launch_bounds__(tpf::kThr)
 tpf_unpack_w_kernel(const int32_t* __restrict__ cnt, const int32_t* __restrict__ ent_pos,
                     const uint16_t* __restrict__ ent_j, int per, int64_t C,
                     const float* __restrict__ wrecv, int64_t wstride, float* __restrict__ w_ent,
-                    int64_t w_cap) {
+                    int64_t w_cap, int groups) {
   using namespace tpf;
   __shared__ uint32_t red[kThr / 64 + 1];
   __shared__ float wj[kUnitK];
-  const int b = blockIdx.x, p = b / per, t = threadIdx.x;
+  const int b = tpf_xcd_group_of(blockIdx.x, groups), p = b / per, t = threadIdx.x;
   const int base = tpf_row_base(cnt, b, per, red);
   const int32_t* c = cnt + 4 * b;
   int off = base;
@@ -2535,17 +2572,18 @@ tpf_pack_grads_kernel(const int32_t* __restrict__ cnt, const int32_t* __restrict
                       int ff, float* __restrict__ gstage, uint32_t* __restrict__ hist,
                       int hist_stripes, double* __restrict__ metrics,
                       int64_t* __restrict__ step_counter, const int32_t* __restrict__ ovf,
-                      int32_t* __restrict__ ovf_host) {
+                      int32_t* __restrict__ ovf_host, int groups) {
   using namespace tpf;
   __shared__ uint32_t red[kThr / 64 + 1];
   __shared__ long long acc[kUnitK];
   __shared__ uint32_t smax;
-  const int b = blockIdx.x, p = b / per, t = threadIdx.x, lane = t & 63;
-  if ((hist || ovf_host) && b == (int)gridDim.x - 1) {  // extra workgroup (the launcher adds it)
+  const int t = threadIdx.x, lane = t & 63;
+  if ((int)blockIdx.x >= groups) {  // extra last workgroup (the launcher adds it)
     if (ovf_host && t == 0) ovf_host[0] = ovf[0];
     if (hist) auc_hist_block(hist, 2048, hist_stripes, metrics, step_counter);
     return;
   }
+  const int b = tpf_xcd_group_of(blockIdx.x, groups), p = b / per;
   const int base = tpf_row_base(cnt, b, per, red);
   const int32_t* c = cnt + 4 * b;
   int32_t* row = send + (int64_t)p * H;
@@ -2638,7 +2676,7 @@ tpf_pack_grads_kernel(const int32_t* __restrict__ cnt, const int32_t* __restrict
         lo = fminf(lo, sl[w]);
         hi = fmaxf(hi, sh[w]);
       }
-      float* part = gstage + (int64_t)(gridDim.x - ((hist || ovf_host) ? 1 : 0)) / per * C;
+      float* part = gstage + (int64_t)(groups / per) * C;
       part[2 * b] = lo;
       part[2 * b + 1] = hi;
     }
@@ -2769,6 +2807,7 @@ static int tpf_groups_of(const TpGeom& g) { return tpf_pair(g) ? g.nbk / 2 : g.n
 int tpf_groups(int64_t n, int bits) { return tpf_groups_of(tp_geom(n, bits)); }
 int tpf_key_region() { return tpf::kUC; }
 int tpf_entry_region() { return tpf::kEC; }
+int tpf_xcd_group(int bid, int groups) { return tpf_xcd_group_of(bid, groups); }
 
 size_t tpf_temp_bytes(int64_t n, int bits) {  // (any minibatch of <= n keys: tpf_stride_max)
   const int64_t N = tpf_stride_max(n);
@@ -2857,8 +2896,9 @@ void tpf_unpack_w(int64_t n, int bits, int G, const int32_t* cnt, const int32_t*
                   const uint16_t* ent_j, int64_t C, const float* wrecv, int64_t wstride,
                   float* w_ent, int64_t w_cap, hipStream_t st) {
   const int per = tpf_per_owner(n, bits, G);
-  tpf_unpack_w_kernel<<<(unsigned)tpf_groups(n, bits), tpf::kThr, 0, st>>>(
-      cnt, ent_pos, ent_j, per, C, wrecv, wstride > 0 ? wstride : C, w_ent, w_cap);
+  const int groups = tpf_groups(n, bits);
+  tpf_unpack_w_kernel<<<(unsigned)groups, tpf::kThr, 0, st>>>(
+      cnt, ent_pos, ent_j, per, C, wrecv, wstride > 0 ? wstride : C, w_ent, w_cap, groups);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
@@ -2869,10 +2909,10 @@ void tpf_pack_grads(int64_t n, int bits, int G, const int32_t* cnt, const int32_
                     int32_t* ovf_host, hipStream_t st) {
   const int per = tpf_per_owner(n, bits, G);
   // (+1 workgroup: the AUC epilogue / overflow publication, off unit 0's critical path)
-  tpf_pack_grads_kernel<<<(unsigned)tpf_groups(n, bits) + ((hist || ovf_host) ? 1u : 0u),
-                          tpf::kThr, 0, st>>>(
+  const int groups = tpf_groups(n, bits);
+  tpf_pack_grads_kernel<<<(unsigned)groups + ((hist || ovf_host) ? 1u : 0u), tpf::kThr, 0, st>>>(
       cnt, ent_pos, ent_j, per, C, kw, H, psum, p_cap, send, ff ? 1 : 0, gstage, hist,
-      hist_stripes, metrics, step_counter, ovf, ovf_host);
+      hist_stripes, metrics, step_counter, ovf, ovf_host, groups);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
@@ -2899,7 +2939,7 @@ void tpf_step(int64_t n, int bits, const int32_t* cntA, const int32_t* posA, con
       cntA != nullptr, cntA, posA, jA, slotA, psum, p_cap, cntB != nullptr, cntB, uniqB, posB,
       jB, slotB, w_ent, w_cap, (Slot*)slots, (uint64_t)(cap - 1), home_base, home_m, 64 - lg,
       init_type, init_v, init_s, seed, err, inserted, p, stats, acc_stripes,
-      cntA ? hist : nullptr, nbins, hist_stripes, metrics, step_counter);
+      cntA ? hist : nullptr, nbins, hist_stripes, metrics, step_counter, groups);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
