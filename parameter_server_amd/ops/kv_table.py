@@ -94,6 +94,11 @@ class KVTable:
         self.num_inserted = 0  # host-side count (CPU path exact; GPU path lazily synced)
 
     # ------------------------------------------------------------------ pull
+    def resolve_args(self) -> tuple:
+        """The trailing arguments every native lookup-or-insert of this table takes (GPU):
+        the init rule, the error word, the insert counter and the ordered-home mapping."""
+        return (*self.init.args(), self._err, self._inserted, self.home_base, self.home_m)
+
     def resolve(self, keys: torch.Tensor, insert: bool = True, with_w: bool = True,
                 n_dev: torch.Tensor | None = None):
         """Lookup-or-insert mixed keys; returns (slot_idx int64, w float32 | None)."""
@@ -101,11 +106,10 @@ class KVTable:
         n = keys.numel()
         slot = torch.empty(n, dtype=torch.int64, device=keys.device)
         w = torch.empty(n, dtype=torch.float32, device=keys.device) if with_w else None
-        it, iv, isd, seed = self.init.args()
         if self.gpu:
-            hipops().kv_resolve(self.slots, keys, n_dev, slot, w, insert, it, iv, isd, seed,
-                                self._err, self._inserted, self.home_base, self.home_m)
+            hipops().kv_resolve(self.slots, keys, n_dev, slot, w, insert, *self.resolve_args())
         else:
+            it, iv, isd, seed = self.init.args()
             ins, full = core().kv_resolve(ptr(self.slots), self.capacity, ptr(keys), n, ptr(slot),
                                           ptr(w), insert, it, iv, isd, seed, self.home_base,
                                           self.home_m)

@@ -17,7 +17,7 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, out_dir, cfg_kw, steps):
+def _worker(rank, world, port, out_dir, cfg_kw, steps, live=None):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
                       WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     torch.set_num_threads(1)
@@ -30,6 +30,9 @@ def _worker(rank, world, port, out_dir, cfg_kw, steps):
     tr = SparseLRTrainer(cfg, comm, dev)
     B = cfg.minibatch
     for s in range(steps):
+        if live is not None and s >= live[rank]:  # this rank's data ran out
+            tr.idle_step()
+            continue
         k, l = criteo_batch(B, seed=100 + rank, row0=s * B, num_features=cfg.num_features,
                             cards=[200] * 26)
         tr.step(k, l)
@@ -39,18 +42,20 @@ def _worker(rank, world, port, out_dir, cfg_kw, steps):
     dist.destroy_process_group()
 
 
-def _run(tmp_path, cfg_kw, steps=4, world=2):
+def _run(tmp_path, cfg_kw, steps=4, world=2, live=None):
     tmp_path.mkdir(parents=True, exist_ok=True)
     port = _free_port()
-    mp.spawn(_worker, args=(world, port, str(tmp_path), cfg_kw, steps), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, port, str(tmp_path), cfg_kw, steps, live), nprocs=world,
+             join=True)
     return [torch.load(tmp_path / f"r{r}.pt", weights_only=False) for r in range(world)]
 
 
-def _reference(cfg_kw, steps, world, lag=0):
+def _reference(cfg_kw, steps, world, lag=0, live=None):
     """Single-process simulation of the protocol: every worker pulls from the same
     model state, then pushes are applied per worker in rank order. ``lag`` = 1: the
     pushes of step s are applied only after the pulls of step s + 1 (SSP, one step
-    of staleness: the padded exchange's pipelined mode)."""
+    of staleness: the padded exchange's pipelined mode). ``live``: rank r contributes
+    nothing (no pull, no push) from step ``live[r]`` on."""
     from parameter_server_amd.models import SparseLRConfig
     from parameter_server_amd.ops import KVTable, linear_backward, linear_forward, localize_torch
     from parameter_server_amd.ops.synthetic import criteo_batch
@@ -63,6 +68,8 @@ def _reference(cfg_kw, steps, world, lag=0):
     for s in range(steps):
         pushes = []
         for r in range(world):
+            if live is not None and s >= live[r]:
+                continue
             k, l = criteo_batch(cfg.minibatch, seed=100 + r, row0=s * cfg.minibatch,
                                 num_features=cfg.num_features, cards=[200] * 26)
             loc = localize_torch(k, bits)
@@ -221,6 +228,41 @@ def test_asp_differs_from_ssp1(tmp_path, merge, lag, algo):
     assert max(abs(merged[k] - ref[k]) for k in ref) < 1e-5
     ssp1 = _reference(cfg_kw, 6, 2, lag=1)
     assert max(abs(merged[k] - ssp1[k]) for k in ref) > 1e-4
+
+
+@pytest.mark.parametrize("consistency,merge,lag,live", [
+    ("bsp", "off", 0, (5, 2)), ("ssp:2", "off", 2, (5, 2)), ("ssp:2", "on", 2, (5, 2)),
+    ("ssp:1", "off", 1, (2, 5)), ("bsp", "off", 0, (5, 0)), ("ssp:3", "on", 3, (6, 3))])
+def test_idle_ranks_match_protocol_reference(tmp_path, consistency, merge, lag, live):
+    """A rank whose data ran out joins the remaining exchanges through ``idle_step()``
+    ((5, 0): from its very first step): it still resolves its peers' pulls, applies
+    their pushes and ships its own last ones. The merged weights are those of the
+    protocol reference in which that rank contributes nothing from step ``live[r]`` on."""
+    steps = max(live)
+    cfg_kw = dict(num_features=1 << 20, minibatch=128, table_capacity=1 << 15, l1=0.5,
+                  consistency=consistency, exchange_merge=merge)
+    res = _run(tmp_path, cfg_kw, steps=steps, world=2, live=live)
+    merged = {}
+    for r in res:
+        for k, w in zip(r["state"]["keys"].tolist(), r["state"]["w"].tolist()):
+            assert k not in merged, "a key lives on exactly one shard"
+            merged[k] = w
+    assert all(r["progress"]["examples"] == sum(live) * 128 for r in res)
+    ref = _reference(cfg_kw, steps, 2, lag=lag, live=live)
+    assert merged.keys() == ref.keys()
+    worst = max(abs(merged[k] - ref[k]) for k in ref)
+    print("largest weight difference", worst)
+    assert worst < 1e-5, worst
+
+
+def test_idle_ranks_asp_runs_and_reports(tmp_path):
+    """asp on two collectives with an idle rank: the run completes and both ranks
+    report every trained example (the owner's asynchronous applies have no single
+    protocol reference to compare with)."""
+    cfg_kw = dict(num_features=1 << 20, minibatch=128, table_capacity=1 << 15, l1=0.5,
+                  consistency="asp", exchange_merge="off")
+    res = _run(tmp_path, cfg_kw, steps=5, world=2, live=(5, 2))
+    assert [r["progress"]["examples"] for r in res] == [896, 896]
 
 
 def test_merged_schedule_rings():

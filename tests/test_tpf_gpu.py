@@ -748,3 +748,39 @@ def test_flat_csr_multi_peer_matches_compact(monkeypatch, merge):
     torch.testing.assert_close(outs[0][1], outs[1][1], rtol=1e-4, atol=1e-5)
     torch.testing.assert_close(outs[0][2], outs[1][2], rtol=1e-4, atol=1e-4)
     assert abs(outs[0][3]["loss"] - outs[1][3]["loss"]) < 1e-4
+
+
+def test_sequential_step_routes_flat_csr_and_generic(monkeypatch):
+    """One trainer, three minibatches through the sequential ``step``: plain (the flat
+    step), valued (the flat CSR step), plain with a prefetch callback (a compact
+    localisation and the generic step). Leaves the table of the compact layout
+    (PSAMD_FLAT=0) fed the same three."""
+    B, N = 256, 1 << 20
+    batches = []
+    for s in range(3):
+        k, lab = criteo_batch(B, seed=83, row0=s * B, num_features=N, device=DEV)
+        batches.append((k, lab))
+    vals = 0.5 + torch.rand(B * 39, device=DEV,
+                            generator=torch.Generator(device=DEV).manual_seed(5))
+    outs = []
+    for flat in ("1", "0"):
+        monkeypatch.setenv("PSAMD_FLAT", flat)
+        cfg = SparseLRConfig(num_features=N, minibatch=B, table_capacity=1 << 16)
+        tr = SparseLRTrainer(cfg, device=DEV)
+        assert (tr.localize_mode == "tpf") == (flat == "1")
+        tr.step(*batches[0], width=39)
+        tr.step(*batches[1], width=39, vals=vals)
+        if flat == "1":
+            assert tr._compact is None  # both ran on the flat layout
+        tr.step(*batches[2], width=39, prefetch=lambda: None)
+        if flat == "1":
+            assert tr._compact is not None  # the generic step, compactly localised
+        p = tr.progress()
+        assert p["examples"] == 3 * B
+        kk, w, z, n = tr.table.occupied()
+        o = torch.argsort(kk)
+        outs.append((kk[o].cpu(), w[o].cpu(), n[o].cpu(), p))
+    assert torch.equal(outs[0][0], outs[1][0])
+    torch.testing.assert_close(outs[0][1], outs[1][1], rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(outs[0][2], outs[1][2], rtol=1e-4, atol=1e-4)
+    assert abs(outs[0][3]["loss"] - outs[1][3]["loss"]) < 1e-4
