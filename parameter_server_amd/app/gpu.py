@@ -28,10 +28,26 @@ torchrun rank is one GPU = a colocated worker + server shard:
 * ``model_output`` -> text ``key\\tweight`` files ``<file>_S<rank>`` (async_sgd.h:160-175,
   bcd.h:251-272).
 
+* ``validation_data`` + ``model_input`` and no ``training_data`` (the reference's
+  ``eval_online.conf`` / ``eval_batch.conf``; the same test app/linear_method makes for the
+  CPU runtime) -> ``run_model_evaluation``: every rank loads the whole model from the
+  ``key\\tweight`` files matching ``model_input.file[0]`` into an HBM table
+  (``ModelScorer.from_text``), the validation files are split over the ranks and stream
+  through ``DeviceFeeder`` once, each minibatch scored by one launch of the fused probe
+  kernel (csrc/hip/predict.hip); rank 0 prints ``evaluation: auc .. accuracy .. examples
+  .. loss ..``. Models written by either trainer (async SGD or Darlin) are scored this
+  way. ``-num_features`` MUST be the value the model was trained with: it sets both the
+  parser's hashing and the key width the table mixes keys over, and a different value
+  silently looks up other keys. A training conf that also has ``validation_data`` is
+  scored once after training from the trainer's own table (``validation:`` line,
+  ``out["validation"]``).
+
 Flags: ``-app_file``, ``-app_conf`` (appended, reference semantics), ``-num_features N``
 (hash keys mod N inside the parser: <= 34-bit keys take the tile localiser; 0 = raw
 64-bit keys), ``-max_nnz_per_example`` (localisation workspace per row, default 128),
-``-num_threads`` (parser threads), ``-device cpu|cuda``, ``-seed``."""
+``-num_threads`` (parser threads), ``-device cpu|cuda``, ``-seed``, ``-minibatch`` (rows
+per scored minibatch of the evaluation route, default 65,536: its conf has no solver block
+to take one from)."""
 from __future__ import annotations
 
 import os
@@ -64,6 +80,8 @@ def _flags(argv):
     # progress lines every this many steps when the step count is agreed up front (a
     # fully cached multi-rank run); 0 = 20 lines per run
     ap.add_argument("-report_steps", "--report_steps", type=int, default=0)
+    # rows per scored minibatch of the evaluation route (run_model_evaluation)
+    ap.add_argument("-minibatch", "--minibatch", type=int, default=65536)
     ap.add_argument("-quiet", "--quiet", action="store_true")
     return ap.parse_args(argv)
 
@@ -211,7 +229,74 @@ def run_async_sgd(lm, comm, device, flags, printer=None) -> dict:
         if d:
             os.makedirs(d, exist_ok=True)
         out["model"] = tr.save_model(mo.file[0])
+    if lm.has("validation_data"):  # score it once with the final weights (collective)
+        out["validation"] = _score_files(tr.scorer(), lm.validation_data, comm, device, flags,
+                                         cfg.minibatch)
+        if rank == 0 and not flags.quiet:
+            print("validation: " + _result_line(out["validation"]), file=sys.stderr)
     return out
+
+
+def _result_line(r: dict) -> str:
+    return (f"auc {r['auc']:.6f} accuracy {r['accuracy']:.6f} examples {r['examples']} "
+            f"loss {r['loss']:.6f}")
+
+
+def _score_files(scorer, data_conf, comm, device, flags, minibatch: int) -> dict:
+    """Stream this rank's share of ``data_conf``'s files through ``scorer`` once, in file
+    order; the result over all ranks (``ModelScorer.result``, collective) plus this
+    rank's own feeder counters."""
+    from ..data import divide_files, search_files
+    from ..data.feeder import DeviceFeeder
+
+    G, rank = comm.world, comm.rank
+    files = search_files(data_conf)
+    if not files:
+        raise FileNotFoundError(f"no validation files match {list(data_conf.file)}")
+    mine = divide_files(files, G, data_conf.max_num_files_per_worker)[rank]
+    cache_dir, _ = _cache_dir(flags, 1, rank)  # (one pass: never a temporary cache)
+    feeder = DeviceFeeder(mine, data_conf.text, minibatch,
+                          minibatch * flags.max_nnz_per_example, device,
+                          num_features=int(flags.num_features), passes=1, shuffle=False,
+                          nthreads=flags.num_threads, ignore_slot=True,
+                          hadoop_home=data_conf.hdfs.home if data_conf.has("hdfs") else "",
+                          max_lines_per_file=data_conf.max_num_lines_per_file,
+                          cache_dir=cache_dir, io_threads=getattr(flags, "io_threads", 16),
+                          parser=getattr(flags, "parser", "cpu"))
+    scorer.evaluate(feeder)
+    res = scorer.result(comm)
+    res.update(rank_examples=feeder.num_examples, h2d_bytes=feeder.bytes_h2d,
+               parser=feeder.parser)
+    return res
+
+
+def run_model_evaluation(lm, comm, device, flags) -> dict:
+    """Score the stored model ``lm.model_input`` on ``lm.validation_data`` (reference
+    ModelEvaluation, model_evaluation.h:9-74, there on the scheduler alone): every rank
+    loads the whole model, the files are split over the ranks, the sums are all-reduced.
+    Returns {"examples", "loss", "accuracy", "auc", "auc_tie_bound", "seconds", ...}."""
+    import torch
+
+    from ..models.scorer import ModelScorer
+    from ..ops.keymix import key_bits_for
+
+    t0 = time.time()
+    bits = key_bits_for(int(flags.num_features))
+    loss = lm.loss.type.lower() if lm.has("loss") else "logit"
+    scorer = ModelScorer.from_text(lm.model_input.file[0], bits, device,
+                                   capacity=getattr(flags, "table_capacity", 0) or None,
+                                   loss=loss)
+    if comm.rank == 0 and not flags.quiet:
+        print(f"loaded {scorer.entries} model entries", file=sys.stderr)
+    res = _score_files(scorer, lm.validation_data, comm, device, flags,
+                       int(getattr(flags, "minibatch", 65536)))
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+    res["seconds"] = time.time() - t0
+    res["model_entries"] = scorer.entries
+    if comm.rank == 0 and not flags.quiet:
+        print("evaluation: " + _result_line(res), file=sys.stderr)
+    return res
 
 
 def _cache_dir(flags, passes: int, rank: int):
@@ -259,6 +344,17 @@ def run_darlin(lm, comm, device, flags, printer=None) -> dict:
     return out
 
 
+def route(lm):
+    """The function that runs ``lm`` (the order of app/linear_method.create_linear_app)."""
+    if lm.has("validation_data") and lm.has("model_input") and not lm.has("training_data"):
+        return run_model_evaluation
+    if lm.has("async_sgd"):
+        return run_async_sgd
+    if lm.has("darlin"):
+        return run_darlin
+    raise ValueError("linear_method needs async_sgd, darlin or validation_data + model_input")
+
+
 def main(argv=None) -> int:
     flags = _flags(sys.argv[1:] if argv is None else argv)
     import torch
@@ -273,12 +369,7 @@ def main(argv=None) -> int:
     dev_type = flags.device if flags.device != "auto" else (
         "cuda" if torch.cuda.is_available() else "cpu")
     comm, device = init_from_env(dev_type)
-    if lm.has("async_sgd"):
-        res = run_async_sgd(lm, comm, device, flags)
-    elif lm.has("darlin"):
-        res = run_darlin(lm, comm, device, flags)
-    else:
-        raise ValueError("linear_method needs async_sgd or darlin")
+    res = route(lm)(lm, comm, device, flags)
     if comm.rank == 0 and not flags.quiet:
         rate = res["examples"] / max(res["seconds"], 1e-9)
         print(f"[psamd] {comm.world} rank(s), rank 0: {res['examples']} examples in "

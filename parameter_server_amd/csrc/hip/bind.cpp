@@ -183,6 +183,10 @@ void criteo_set_tables(const uint32_t*, const float*);
 void criteo_gen(uint64_t, int64_t, const int64_t*, int64_t, int64_t, uint64_t, float, uint64_t*,
                 float*, int64_t*, hipStream_t);
 void add_i64(int64_t*, int64_t, hipStream_t);
+// predict.hip
+void predict_rows(const void*, int64_t, uint64_t, uint64_t, KeyMix, const uint64_t*, int64_t,
+                  const int64_t*, int, const float*, const float*, int64_t, int, float*, double*,
+                  int, unsigned long long*, int, int, int, hipStream_t);
 // filters.hip
 void cm_insert(uint32_t*, uint64_t, int, int, uint32_t, const uint64_t*, const uint8_t*, int64_t,
                const int32_t*, hipStream_t);
@@ -2079,6 +2083,43 @@ PYBIND11_MODULE(_hipops, m) {
                       hp ? (int)std::max<int64_t>(1, hist->numel() / (2 * nbins)) : 1,
                       cur_stream());
   });
+  // Score a minibatch of raw keys against a slot table (predict.hip): margin[B], the
+  // striped [loss, correct, count] sums and the u64 striped AUC histogram, each optional.
+  // lanes: lanes per row, 0 = from nnz / B (predict.hip predict_lanes), else 8 or 64.
+  m.def("predict_rows", [](Tensor slots, uint64_t home_base, uint64_t home_m, Tensor keys,
+                           int bits, optional<Tensor> row_ptr, int width, optional<Tensor> vals,
+                           optional<Tensor> labels, int64_t B, int loss_type,
+                           optional<Tensor> margin, optional<Tensor> metrics,
+                           optional<Tensor> hist, int nbins, int lanes) {
+    const int64_t cap = slot_capacity(slots);
+    chk(keys, at::kLong, "keys");
+    const int64_t nnz = keys.numel();
+    check(B >= 0, "predict_rows: B >= 0");
+    const int64_t* rp = optr<int64_t>(row_ptr, at::kLong, "row_ptr");
+    if (rp) check(row_ptr->numel() >= B + 1, "row_ptr too small");
+    else check(width > 0 && B <= nnz / width, "fixed width layout too small");
+    const float* v = optr<float>(vals, at::kFloat, "vals");
+    if (v) check(vals->numel() >= nnz, "vals too small");
+    const float* lb = optr<float>(labels, at::kFloat, "labels");
+    if (lb) check(labels->numel() >= B, "labels too small");
+    float* mg = optr<float>(margin, at::kFloat, "margin");
+    if (mg) check(margin->numel() >= B, "margin too small");
+    double* mp = optr<double>(metrics, at::kDouble, "metrics");
+    if (mp) check(lb && metrics->numel() >= 3, "metrics needs labels and >= 3 slots");
+    unsigned long long* hp = optr<unsigned long long>(hist, at::kLong, "hist");
+    if (hp) check(lb && nbins > 0 && nbins <= 8192 && hist->numel() >= 2 * nbins &&
+                      hist->numel() % (2 * nbins) == 0,
+                  "hist needs labels and int64 [stripes x 2 x nbins], nbins <= 8192");
+    check(lanes == 0 || lanes == 8 || lanes == 64, "lanes per row: 0 (auto), 8 or 64");
+    check(loss_type >= 1 && loss_type <= 4, "loss type in [1, 4]");
+    psamd::predict_rows(slots.data_ptr(), cap, home_base, home_m, make_keymix(bits),
+                        ptr<uint64_t>(keys), nnz, rp, width, v, lb, B, loss_type, mg, mp,
+                        acc_stripes_of(metrics), hp, nbins,
+                        hp ? (int)(hist->numel() / (2 * nbins)) : 1, lanes, cur_stream());
+  }, py::arg("slots"), py::arg("home_base"), py::arg("home_m"), py::arg("keys"), py::arg("bits"),
+     py::arg("row_ptr"), py::arg("width"), py::arg("vals"), py::arg("labels"), py::arg("B"),
+     py::arg("loss_type"), py::arg("margin"), py::arg("metrics"), py::arg("hist"),
+     py::arg("nbins"), py::arg("lanes") = 0);
   m.def("linear_bwd", [](Tensor pos_s, Tensor segid, int64_t n, optional<Tensor> rows, int width,
                          optional<Tensor> vals, Tensor coef, optional<Tensor> coef2, Tensor grad,
                          optional<Tensor> hess) {

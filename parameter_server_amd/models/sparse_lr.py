@@ -900,3 +900,49 @@ class SparseLRTrainer(PaddedExchange, ExactExchange, P2PExchange):
         self.table.load(keys[own], sd["w"].to(self.device)[own], sd["z"].to(self.device)[own],
                         sd["n"].to(self.device)[own])
         self.step_count = int(sd.get("step", 0))
+
+    # ------------------------------------------------------------ scoring
+    def scorer(self):
+        """A ``ModelScorer`` (models/scorer.py) over the current weights, after ``flush()``.
+        Collective when G > 1.
+
+        One rank: the trainer's own table, aliased (zero copy, ordered homes honoured); it
+        sees later steps too, after their ``flush()``. G > 1: a REPLICA of the whole model
+        on every rank, as scoring probes every key locally -- each rank takes the non-zero
+        (mixed key, w) of its shard, the ranks all-gather them (counts, then rows padded to
+        the largest shard) and each loads the union into a scratch hashed-home table at
+        load <= 0.5. That costs 32 B per slot, i.e. 64-128 B per non-zero weight of the
+        WHOLE model on every rank; ``KVTable.check_ok`` raises if it does not fit."""
+        from .scorer import ModelScorer
+
+        self.flush()
+        if self.G == 1 or self._loopback:
+            return ModelScorer.from_table(self.table, self.bits, self.cfg.loss)
+        keys, w, _, _ = self.table.occupied()
+        nz = w != 0
+        keys, w = keys[nz].contiguous(), w[nz].contiguous()
+        counts = self.comm.all_gather_counts(
+            torch.tensor([keys.numel()], dtype=torch.int64)).reshape(-1).tolist()
+        C = max(1, max(counts))
+        dev = keys.device
+        pk = torch.zeros(C, dtype=torch.int64, device=dev)
+        pw = torch.zeros(C, dtype=torch.float32, device=dev)
+        pk[:keys.numel()] = keys
+        pw[:w.numel()] = w
+        ak = torch.empty(self.G * C, dtype=torch.int64, device=dev)
+        aw = torch.empty(self.G * C, dtype=torch.float32, device=dev)
+        self.comm.all_gather_into_async(ak, pk).wait()
+        self.comm.all_gather_into_async(aw, pw).wait()
+        sel = torch.cat([torch.arange(r * C, r * C + n, device=dev)
+                         for r, n in enumerate(counts)])
+        return ModelScorer.from_pairs(ak[sel], aw[sel], self.bits, self.device,
+                                      loss=self.cfg.loss)
+
+    def evaluate(self, feeder, comm=None) -> dict:
+        """Score one pass of a ``DeviceFeeder`` with the current weights; the result dict
+        of ``ModelScorer.result`` (over all ranks of ``comm`` when given)."""
+        return self.scorer().evaluate(feeder).result(comm)
+
+    def predict(self, keys: torch.Tensor, *, row_ptr=None, width=None, vals=None):
+        """Margins of raw-key rows under the current weights (``ModelScorer.predict``)."""
+        return self.scorer().predict(keys, row_ptr=row_ptr, width=width, vals=vals)
