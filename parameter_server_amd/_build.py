@@ -66,9 +66,10 @@ def build_hipops(jobs: int = 8, verbose: bool = False) -> Path:
     src_dir = CSRC / "hip"
     out_dir = BUILD / "hip"
     out_dir.mkdir(parents=True, exist_ok=True)
-    # (textparse.hip includes the scanners it shares with the host runtime)
+    # (textparse.hip / modeltext.hip include the scanners and the formatter they share with
+    # the host runtime)
     headers = sorted(src_dir.glob("*.cuh")) + sorted(src_dir.glob("*.h")) + \
-        [CSRC / "core" / "textnum.h"]
+        [CSRC / "core" / "textnum.h", CSRC / "core" / "textfmt.h"]
     common = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", str(src_dir),
               "-Wno-unused-result", "-Wno-deprecated-declarations"]
     jobs_list = []

@@ -229,6 +229,7 @@ def run_async_sgd(lm, comm, device, flags, printer=None) -> dict:
         if d:
             os.makedirs(d, exist_ok=True)
         out["model"] = tr.save_model(mo.file[0])
+        out["model_deferred_chunks"] = tr.last_save["deferred_chunks"]
     if lm.has("validation_data"):  # score it once with the final weights (collective)
         out["validation"] = _score_files(tr.scorer(), lm.validation_data, comm, device, flags,
                                          cfg.minibatch)
@@ -294,6 +295,7 @@ def run_model_evaluation(lm, comm, device, flags) -> dict:
         torch.cuda.synchronize(device)
     res["seconds"] = time.time() - t0
     res["model_entries"] = scorer.entries
+    res["model_deferred_chunks"] = scorer.deferred_chunks  # (text the host rules parsed)
     if comm.rank == 0 and not flags.quiet:
         print("evaluation: " + _result_line(res), file=sys.stderr)
     return res

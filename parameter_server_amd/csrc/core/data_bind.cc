@@ -3,10 +3,14 @@
 #include <pybind11/stl.h>
 
 #include <algorithm>
+#include <cstring>
+#include <stdexcept>
+#include <string>
 #include <type_traits>
 
 #include "data.h"
 #include "module_parts.h"
+#include "textfmt.h"
 #include "textnum.h"
 
 namespace py = pybind11;
@@ -150,6 +154,26 @@ void register_data(py::module_& m) {
       st.mutable_data()[i] = textnum::criteo_bucket(v.data()[i], &ids.mutable_data()[i]);
     }
     return py::make_tuple(ids, st);
+  });
+  // Test-only entry point of the model-text formatter shared with the device
+  // (csrc/core/textfmt.h): (text of the kOk entries back to back, status, length) per entry.
+  m.def("textfmt_entries", [](py::array_t<uint64_t, py::array::c_style> keys,
+                              py::array_t<float, py::array::c_style> w) {
+    if (keys.size() != w.size()) throw std::invalid_argument("textfmt_entries: sizes differ");
+    const py::ssize_t n = keys.size();
+    py::array_t<int32_t> st(n), len(n);
+    std::string text;
+    text.reserve((size_t)n * 24);
+    uint8_t buf[textfmt::kMaxEntry];
+    for (py::ssize_t i = 0; i < n; ++i) {
+      uint32_t bits;
+      std::memcpy(&bits, &w.data()[i], 4);
+      int l = 0;
+      st.mutable_data()[i] = textfmt::put_entry(keys.data()[i], bits, buf, &l);
+      len.mutable_data()[i] = l;
+      text.append((const char*)buf, (size_t)l);
+    }
+    return py::make_tuple(py::bytes(text), st, len);
   });
   m.attr("RECORDIO_MAGIC") = kRecordIOMagic;
 }

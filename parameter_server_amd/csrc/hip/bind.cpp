@@ -268,6 +268,14 @@ void textparse(const uint8_t*, int64_t, int, uint64_t, int64_t, int64_t, float*,
                int64_t, uint64_t*, float*, int64_t, int32_t*, int32_t*, hipStream_t);
 void textparse_rebase(const int64_t*, int64_t*, int64_t, int64_t, hipStream_t);
 void textparse_seg_nonunit(const float*, int64_t, const int64_t*, int, int32_t*, hipStream_t);
+void modeltext_parse(const uint8_t*, int64_t, uint64_t*, float*, int64_t, int32_t*, int32_t*,
+                     hipStream_t);
+// modeltext.hip
+int64_t modeltext_block();
+int64_t modeltext_max_entry();
+int64_t modeltext_work_bytes(int64_t);
+void modeltext_format(const uint64_t*, const uint32_t*, int64_t, uint8_t*, int64_t, int64_t*,
+                      uint8_t*, hipStream_t);
 }  // namespace psamd
 
 using at::Tensor;
@@ -1879,6 +1887,41 @@ PYBIND11_MODULE(_hipops, m) {
     psamd::textparse_seg_nonunit(ptr<float>(vals), vals.numel(), ptr<int64_t>(bounds), (int)nseg,
                                  ptr<int32_t>(flags), cur_stream());
   });
+
+  // ---------------- model text ----------------
+  m.def("modeltext_block", [] { return psamd::modeltext_block(); });
+  m.def("modeltext_max_entry", [] { return psamd::modeltext_max_entry(); });
+  m.def("modeltext_work_bytes", [](int64_t n) { return psamd::modeltext_work_bytes(n); });
+  m.def("modeltext_format", [](Tensor keys, Tensor w, Tensor out, Tensor hdr, Tensor work) {
+    chk(keys, at::kLong, "keys");
+    chk(w, at::kFloat, "w");
+    chk(out, at::kByte, "out");
+    chk(hdr, at::kLong, "hdr");
+    chk(work, at::kByte, "work");
+    const int64_t n = keys.numel();
+    check(n >= 1 && w.numel() == n, "modeltext_format: keys and w must be equally long, not empty");
+    check(out.numel() >= n * psamd::modeltext_max_entry(), "modeltext_format: out too small");
+    check(hdr.numel() >= 3, "modeltext_format: header needs 3 words");
+    check(work.numel() >= psamd::modeltext_work_bytes(n), "modeltext_format: work buffer too small");
+    psamd::modeltext_format(ptr<uint64_t>(keys), reinterpret_cast<const uint32_t*>(ptr<float>(w)), n,
+                            ptr<uint8_t>(out), out.numel(), ptr<int64_t>(hdr), ptr<uint8_t>(work),
+                            cur_stream());
+  }, py::arg("keys"), py::arg("w"), py::arg("out"), py::arg("hdr"), py::arg("work"));
+  m.def("modeltext_parse", [](Tensor text, int64_t n, Tensor keys, Tensor w, Tensor hdr,
+                              Tensor work) {
+    chk(text, at::kByte, "text");
+    chk(keys, at::kLong, "keys");
+    chk(w, at::kFloat, "w");
+    chk(hdr, at::kInt, "hdr");
+    chk(work, at::kInt, "work");
+    check(n >= 1 && n <= text.numel(), "modeltext_parse: n outside the text buffer");
+    check(hdr.numel() >= 8, "modeltext_parse: header needs 8 words");
+    check(work.numel() >= psamd::textparse_work_words(n), "modeltext_parse: work buffer too small");
+    const int64_t cap = std::min<int64_t>(keys.numel(), w.numel());
+    check(cap >= 1, "modeltext_parse: empty outputs");
+    psamd::modeltext_parse(ptr<uint8_t>(text), n, ptr<uint64_t>(keys), ptr<float>(w), cap,
+                           ptr<int32_t>(hdr), ptr<int32_t>(work), cur_stream());
+  }, py::arg("text"), py::arg("n"), py::arg("keys"), py::arg("w"), py::arg("hdr"), py::arg("work"));
 
   // ---------------- localisation ----------------
   m.def("mix_iota", [](Tensor keys, int bits, Tensor h, Tensor pos) {

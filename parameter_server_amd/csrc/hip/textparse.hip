@@ -24,6 +24,8 @@
 //   4. tp_finish  non-decreasing LIBSVM indices (a descent is legal only at a row start:
 //                 only descents search row_ptr), min / max row width, then keys mod
 //                 hash_mod in a launch of its own (tp_mod: the check reads raw keys).
+// The same count / scan / emit launches read key<TAB>weight model files (modeltext_parse,
+// an internal format: rows are a key token and a weight token, no row offsets, no finish).
 // Text traffic: the text is read twice (count, emit); outputs are written once, the keys
 // re-read once (and rewritten when hash_mod != 0), row_ptr re-read once.
 //
@@ -46,6 +48,9 @@ constexpr int kTpBytes = 16;                // text bytes per thread
 constexpr int kTpSpan = kTpBlk * kTpBytes;  // 16 KiB of text per workgroup
 constexpr int kTpWaves = kTpBlk / kWave;
 constexpr int kFmtLibsvm = 5, kFmtCriteo = 8;  // data.TEXT_FORMATS
+// Internal: key<TAB>weight model lines (modeltext_parse below; not a data.TEXT_FORMATS id).
+// Tokens as in LIBSVM; a row is a key token and its weight token, nothing else.
+constexpr int kFmtModel = 100;
 
 // header words (int32)
 enum { H_ROWS, H_NNZ, H_MINW, H_MAXW, H_NONUNIT, H_BAD, H_DEFER, H_CAP, H_WORDS };
@@ -159,10 +164,11 @@ __device__ __forceinline__ void tp_classify(const uint8_t* __restrict__ text, in
   }
   const uint32_t p_nl = prev == '\n', p_tab = prev == '\t', p_bl = (prev == ' ') | (prev == '\r');
   uint32_t ts, anom = 0;
-  if (kFmt == kFmtLibsvm) {
+  if (kFmt == kFmtLibsvm || kFmt == kFmtModel) {
     // separators: blank, tab, CR; a token starts after a separator or a newline
     const uint32_t p_tok = !(p_nl | p_tab | p_bl);
     ts = tk & ~((tk << 1) | p_tok);
+    if (kFmt == kFmtModel) anom = blank;  // (a blank or CR anywhere: the host decides)
   } else {
     // fields end at tab / newline only; blanks are trimmed at a field's END, so content
     // after a blank inside a field is a malformed field (or a field past the 39th)
@@ -239,6 +245,7 @@ __device__ __forceinline__ void tp_classify(const uint8_t* __restrict__ text, in
     blk.tabseg = seg_tot;
     blk.anom = (uint32_t)__syncthreads_or((int)anom) ? 1u : 0u;
   }
+  if (kFmt == kFmtModel) blk.anom = (uint32_t)__syncthreads_or((int)anom) ? 1u : 0u;
 }
 
 template <int kFmt>
@@ -312,7 +319,7 @@ __global__ void __launch_bounds__(kTpBlk) tp_scan_kernel(const int32_t* __restri
     hdr[H_BAD] = 0;
     hdr[H_DEFER] = (int32_t)anom;
     if (over) hdr[H_CAP] = 1;  // (sticky: only the caller clears it)
-    else row_ptr[row0 + rows] = nnz0 + nnz;
+    else if (row_ptr) row_ptr[row0 + rows] = nnz0 + nnz;  // (model lines keep no offsets)
   }
 }
 
@@ -355,7 +362,7 @@ __global__ void __launch_bounds__(kTpBlk) tp_emit_kernel(
     for (; len < lim; ++len) {
       const uint32_t c = p[len];
       if (c == '\n' || c == '\t') break;
-      if (kFmt == kFmtLibsvm) {
+      if (kFmt == kFmtLibsvm || kFmt == kFmtModel) {
         if (c == ' ' || c == '\r') break;
         if (c == ':' && colon < 0) colon = len;
       }
@@ -387,6 +394,40 @@ __global__ void __launch_bounds__(kTpBlk) tp_emit_kernel(
           if (v != 1.f) nonunit = 1;
         }
       }
+    } else if (kFmt == kFmtModel) {
+      // A plain line is digits, one tab, a weight, then '\n' or the end of the text; all of
+      // it is decided per token from the bytes next to it. A key must open its line and be
+      // followed by a tab and the first byte of a token; a weight must follow a tab and end
+      // its line. A weight that ends its line is the line's last token and a key has one
+      // right behind it, so when every token passes, every row is one key and one weight
+      // and the weight of row R is feature R.
+      const auto byte_at = [&](int64_t gg) -> uint32_t {
+        if (gg < 0 || gg >= n) return '\n';
+        const int64_t q = gg - base;
+        return (q >= 0 && q < kTpSpan) ? lds_text[q] : text[gg];
+      };
+      const uint32_t before = byte_at(g - 1), after = byte_at(g + len);
+      if (is_lab) {
+        const uint32_t nx = byte_at(g + len + 1);
+        uint64_t k = 0;
+        if (before != '\n' || after != '\t' || nx == '\n' || nx == '\t' || nx == ' ' ||
+            nx == '\r') {
+          st = textnum::kDefer;
+        } else {
+          st = textnum::scan_u64(p, len, &k);
+          if (st == textnum::kOk && in_range(row0 + R, cap_rows)) keys[row0 + R] = k;
+        }
+      } else {
+        float v = 0.f;
+        // (the scanner takes "+-5"; Python's float takes "+5" and not "+-5": the host decides)
+        if (before != '\t' || after != '\n' || p[0] == '+') {
+          st = textnum::kDefer;
+        } else {
+          st = textnum::scan_f32(p, len, &v);
+          if (st == textnum::kOk && in_range(row0 + R, cap_rows)) vals[row0 + R] = v;
+        }
+      }
+      if (st == textnum::kBad) st = textnum::kDefer;  // (Python takes "1_0" and "nan")
     } else {
       while (len > 0 && (p[len - 1] == ' ' || p[len - 1] == '\r')) --len;  // (trailing blanks)
       const uint32_t below = (1u << i) - 1u;
@@ -537,6 +578,26 @@ void textparse(const uint8_t* text, int64_t n, int fmt, uint64_t hash_mod, int64
   }
   tp_finish_kernel<<<fgrid, 256, 0, st>>>(keys, row_ptr, row0, nnz0, fmt == kFmtLibsvm, hdr);
   if (hash_mod) tp_mod_kernel<<<fgrid, 256, 0, st>>>(keys, nnz0, hash_mod, hdr);
+  PSAMD_HIP_CHECK(hipGetLastError());
+}
+
+// key<TAB>weight model text (utils/checkpoint.py): keys[r] / w[r] of line r, in file order.
+// The chunk counts only if hdr reports no H_CAP / H_BAD / H_DEFER and H_ROWS == H_NNZ; else
+// the caller parses it by the host rules. text: n bytes, 16-byte aligned, starting at a line
+// start. hdr / work as for textparse.
+void modeltext_parse(const uint8_t* text, int64_t n, uint64_t* keys, float* w, int64_t cap,
+                     int32_t* hdr, int32_t* work, hipStream_t st) {
+  if (n <= 0 || n > ((int64_t)1 << 30))
+    throw std::invalid_argument("modeltext_parse: chunk size must be in [1, 2^30] bytes");
+  if (((uintptr_t)text & 15) != 0)
+    throw std::invalid_argument("modeltext_parse: text buffer must be 16-byte aligned");
+  const int64_t nb = (n + kTpSpan - 1) / kTpSpan;
+  int32_t* sum = work;
+  int32_t* bases = work + nb * S_WORDS;
+  tp_count_kernel<kFmtModel><<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, sum);
+  tp_scan_kernel<<<1, kTpBlk, 0, st>>>(sum, bases, nb, 0, 0, cap, cap + 1, cap, nullptr, hdr);
+  tp_emit_kernel<kFmtModel><<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, bases, 0, 0, cap, cap,
+                                                            nullptr, nullptr, keys, w, hdr);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 

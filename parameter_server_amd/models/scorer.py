@@ -10,7 +10,6 @@ minibatches and ranks; ``result`` turns them into the figures.
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 
 from ..ops.keymix import mix
@@ -44,19 +43,33 @@ class ModelScorer:
 
     @classmethod
     def from_text(cls, pattern: str, bits: int, device, capacity: int | None = None,
-                  loss="logit") -> "ModelScorer":
+                  loss="logit", text_io: str = "auto") -> "ModelScorer":
         """Every ``key\\tweight`` file matching ``pattern`` (regex or glob,
         utils/checkpoint.read_text_models). ``bits`` must be the key width the model was
-        trained with (``key_bits_for(num_features)``)."""
+        trained with (``key_bits_for(num_features)``). ``text_io``: "device" parses the
+        text on the GPU (ops/modeltext.py; the same weights), "host" is the dict reader,
+        "auto" the device path when ``device`` is a GPU. ``deferred_chunks`` counts the
+        chunks of text the device parser left to the host rules."""
+        from ..ops.modeltext import pairs_of, read_text_models_device
         from ..utils.checkpoint import read_text_models
 
-        model = read_text_models(pattern)
-        raw = torch.from_numpy(np.fromiter(model.keys(), dtype=np.uint64,
-                                           count=len(model)).view(np.int64).copy())
-        w = torch.tensor(list(model.values()), dtype=torch.float64).float()
+        if text_io not in ("auto", "host", "device"):
+            raise ValueError(f"from_text: text_io must be auto, host or device, not {text_io!r}")
         dev = torch.device(device)
+        if text_io == "device" and dev.type != "cuda":
+            raise ValueError("from_text: text_io='device' needs a GPU device")
+        if text_io != "host" and dev.type == "cuda":
+            raw, w, entries, deferred = read_text_models_device(pattern, dev)
+            sc = cls.from_pairs(mix(raw, bits), w, bits, dev, capacity, loss)
+            # a repeated key: the dict reader lets the later line win, scattered writes
+            # promise no order, so the whole load goes through the dict reader
+            if entries == 0 or sc.table.census()[0] == entries:
+                sc.entries, sc.deferred_chunks = entries, deferred
+                return sc
+            del sc
+        raw, w = pairs_of(read_text_models(pattern))
         sc = cls.from_pairs(mix(raw.to(dev), bits), w, bits, dev, capacity, loss)
-        sc.entries = len(model)
+        sc.entries, sc.deferred_chunks = raw.numel(), 0
         return sc
 
     # ------------------------------------------------------------ scoring

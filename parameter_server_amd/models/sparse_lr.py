@@ -872,17 +872,30 @@ class SparseLRTrainer(PaddedExchange, ExactExchange, P2PExchange):
         return out
 
     # ------------------------------------------------------------ checkpoint
-    def save_model(self, prefix: str, node_id: str | None = None) -> str:
+    def save_model(self, prefix: str, node_id: str | None = None, text_io: str = "auto") -> str:
         """Reference checkpoint layout: ``<prefix>_<NodeID>`` with one ``key\\tweight``
-        line per non-zero weight (src/parameter/kv_store.h:63-73)."""
+        line per non-zero weight (src/parameter/kv_store.h:63-73). ``text_io``: "device"
+        formats the text on the GPU (ops/modeltext.py; the same bytes), "host" is
+        ``utils/checkpoint.write_text_model``, "auto" the device path when the table is on a
+        GPU. ``last_save`` holds the entry count and the chunks the device formatter left
+        to the host."""
+        from ..ops.modeltext import write_text_model_device
         from ..utils.checkpoint import write_text_model
 
+        if text_io not in ("auto", "host", "device"):
+            raise ValueError(f"save_model: text_io must be auto, host or device, not {text_io!r}")
+        if text_io == "device" and not self.table.gpu:
+            raise ValueError("save_model: text_io='device' needs the table on a GPU")
         self.flush()
 
-        keys, w, _, _ = self.table.occupied()
+        keys, w = self.table.occupied_weights()
         raw = unmix(keys, self.bits)
         path = f"{prefix}_{node_id or f'S{self.rank}'}"
-        write_text_model(path, raw.cpu(), w.cpu())
+        if text_io != "host" and self.table.gpu:
+            entries, deferred = write_text_model_device(path, raw, w)
+        else:
+            entries, deferred = write_text_model(path, raw.cpu(), w.cpu()), 0
+        self.last_save = {"path": path, "entries": entries, "deferred_chunks": deferred}
         return path
 
     def state_dict(self) -> dict:

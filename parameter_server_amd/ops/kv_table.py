@@ -171,6 +171,20 @@ class KVTable:
             return parts[0]
         return tuple(torch.cat([p[i] for p in parts]) for i in range(4))
 
+    def occupied_weights(self, chunk: int = 1 << 27):
+        """(mixed keys, w) of every occupied slot (device tensors): ``occupied`` without
+        the copies of z and n, for a model save."""
+        parts = []
+        for a in range(0, self.capacity, chunk):
+            sl = self.slots[a:a + chunk]
+            keys = sl[:, 0]
+            mask = keys != EMPTY_KEY
+            w = sl[:, 1].contiguous().view(torch.float32)[0::2]  # (the low word of w | z)
+            parts.append((keys[mask], w[mask]))
+        if len(parts) == 1:
+            return parts[0]
+        return tuple(torch.cat([p[i] for p in parts]) for i in range(2))
+
     def load(self, keys_mixed: torch.Tensor, w, z=None, n=None):
         slot, _ = self.resolve(keys_mixed.to(self.device), insert=True, with_w=False)
         self.set(slot, w.to(self.device).float().contiguous(),

@@ -16,6 +16,13 @@ import numpy as np
 import torch
 
 
+def text_model_lines(k, v):
+    """The ``key\\tweight`` lines of uint64 keys ``k`` and float weights ``v`` (numpy arrays),
+    one string per entry, in the order given."""
+    for kk, vv in zip(k, v):
+        yield f"{int(kk)}\t{float(vv):.9g}\n"
+
+
 def write_text_model(path: str, keys, w) -> int:
     """``keys``: uint64 (or int64 bit pattern) tensor / array; ``w``: float tensor / array."""
     d = os.path.dirname(path)
@@ -30,27 +37,38 @@ def write_text_model(path: str, keys, w) -> int:
     v = v[keep]
     order = np.argsort(k, kind="stable")
     with open(path, "w") as f:
-        for kk, vv in zip(k[order], v[order]):
-            f.write(f"{int(kk)}\t{float(vv):.9g}\n")
+        f.writelines(text_model_lines(k[order], v[order]))
     return int(keep.sum())
 
 
-def read_text_models(pattern: str) -> dict[int, float]:
-    """Load every ``key\\tweight`` file matching a regex / glob (model_evaluation.h:22-33)."""
+def find_model_files(pattern: str) -> list[str]:
+    """The files a model pattern names, in load order: the sorted glob matches, or, when the
+    glob matches nothing, the directory entries whose name the pattern's last component
+    matches as a regex (model_evaluation.h:22-33)."""
     files = sorted(glob.glob(pattern))
     if not files:
         d = os.path.dirname(pattern) or "."
         rx = re.compile(os.path.basename(pattern))
         files = sorted(os.path.join(d, f) for f in os.listdir(d) if rx.fullmatch(f) or rx.match(f))
+    return files
+
+
+def parse_model_lines(lines, model: dict[int, float]) -> None:
+    """``model[key] = weight`` of every non-empty ``key\\tweight`` line (a later line wins)."""
+    for line in lines:
+        line = line.strip()
+        if not line:
+            continue
+        k, v = line.split("\t")
+        model[int(k)] = float(v)
+
+
+def read_text_models(pattern: str) -> dict[int, float]:
+    """Load every ``key\\tweight`` file matching a regex / glob (model_evaluation.h:22-33)."""
     model: dict[int, float] = {}
-    for fn in files:
+    for fn in find_model_files(pattern):
         with open(fn) as f:
-            for line in f:
-                line = line.strip()
-                if not line:
-                    continue
-                k, v = line.split("\t")
-                model[int(k)] = float(v)
+            parse_model_lines(f, model)
     return model
 
 
