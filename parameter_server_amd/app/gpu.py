@@ -45,7 +45,9 @@ torchrun rank is one GPU = a colocated worker + server shard:
 Flags: ``-app_file``, ``-app_conf`` (appended, reference semantics), ``-num_features N``
 (hash keys mod N inside the parser: <= 34-bit keys take the tile localiser; 0 = raw
 64-bit keys), ``-max_nnz_per_example`` (localisation workspace per row, default 128),
-``-num_threads`` (parser threads), ``-device cpu|cuda``, ``-seed``, ``-minibatch`` (rows
+``-num_threads`` (parser threads), ``-device cpu|cuda``, ``-seed``, ``-table_capacity``
+(slots per shard; 0 = sized from ``-num_features``), ``-table_growth on`` (the table grows
+on the device before it fills, so the capacity is only where it starts), ``-minibatch`` (rows
 per scored minibatch of the evaluation route, default 65,536: its conf has no solver block
 to take one from)."""
 from __future__ import annotations
@@ -67,6 +69,9 @@ def _flags(argv):
     ap.add_argument("-device", "--device", default="auto")
     ap.add_argument("-seed", "--seed", type=int, default=0)
     ap.add_argument("-table_capacity", "--table_capacity", type=int, default=0)
+    # "on": the trainer's table is rehashed into a larger one before it fills
+    # (SparseLRConfig.table_growth), so -table_capacity is only where it starts
+    ap.add_argument("-table_growth", "--table_growth", choices=("off", "on"), default="off")
     # binary example cache (data/bincache.py): "" = $PSAMD_DATA_CACHE, else a private
     # temporary one when num_data_pass > 1; "off" = parse the text on every pass
     ap.add_argument("-data_cache", "--data_cache", default="")
@@ -127,6 +132,8 @@ def run_async_sgd(lm, comm, device, flags, printer=None) -> dict:
                 seed=flags.seed + rank)
     if flags.table_capacity:
         over["table_capacity"] = flags.table_capacity
+    if getattr(flags, "table_growth", "off") == "on":
+        over["table_growth"] = True
     if G > 1 and sgd.max_delay <= 0:
         over["consistency"] = "asp"  # the reference's unbounded pipelining (async_sgd.h:219-238)
     cfg = lm_to_sparse_lr(lm, **over)
@@ -218,7 +225,8 @@ def run_async_sgd(lm, comm, device, flags, printer=None) -> dict:
            "text_passes": feeder.text_passes, "cached_passes": feeder.cached_passes,
            "parser": feeder.parser, "text_chunks": feeder.text_chunks,
            "deferred_chunks": feeder.deferred_chunks,
-           "agreed_steps": agreed, "host_feed_wait_s": t_feed, "host_step_issue_s": t_step}
+           "agreed_steps": agreed, "host_feed_wait_s": t_feed, "host_step_issue_s": t_step,
+           "table_capacity": p["table_capacity"], "table_grown": p["table_grown"]}
     if tmp_cache:
         import shutil
 
@@ -376,6 +384,8 @@ def main(argv=None) -> int:
         rate = res["examples"] / max(res["seconds"], 1e-9)
         print(f"[psamd] {comm.world} rank(s), rank 0: {res['examples']} examples in "
               f"{res['seconds']:.2f} s ({rate:.3g} examples/s)"
+              + (f", table {res['table_capacity']} slots (grown {res['table_grown']} times)"
+                 if "table_capacity" in res else "")
               + (f", model {res['model']}" if "model" in res else ""), file=sys.stderr)
     import torch.distributed as dist
 

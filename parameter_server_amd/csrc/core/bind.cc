@@ -53,6 +53,21 @@ PYBIND11_MODULE(_pscore, m) {
   }, py::arg("slots"), py::arg("cap"), py::arg("keys"), py::arg("n"), py::arg("out_slot"),
      py::arg("out_w"), py::arg("insert"), py::arg("init_type"), py::arg("init_v"),
      py::arg("init_s"), py::arg("seed"), py::arg("home_base") = 0, py::arg("home_m") = 0);
+  m.def("kv_rehash", [](uintptr_t old_slots, int64_t old_cap, uintptr_t slots, int64_t cap,
+                        uint64_t home_base, uint64_t home_m) {
+    if (cap <= 0 || (cap & (cap - 1)) || old_cap <= 0 || (old_cap & (old_cap - 1)))
+      throw std::invalid_argument("capacity must be 2^k");
+    if (cap < old_cap) throw std::invalid_argument("kv_rehash: the new table must not be smaller");
+    bool full = false;
+    int64_t moved;
+    {
+      py::gil_scoped_release rel;
+      moved = kv_rehash(P<const Slot>(old_slots), old_cap, P<Slot>(slots), cap, home_base, home_m,
+                        &full);
+    }
+    return py::make_tuple(moved, full);
+  }, py::arg("old_slots"), py::arg("old_cap"), py::arg("slots"), py::arg("cap"),
+     py::arg("home_base") = 0, py::arg("home_m") = 0);
   m.def("kv_gather", [](uintptr_t slots, uintptr_t idx, int64_t n, uintptr_t out, int field) {
     py::gil_scoped_release rel;
     kv_gather(P<const Slot>(slots), P<const int64_t>(idx), n, P<float>(out), field);

@@ -109,6 +109,32 @@ int64_t kv_resolve(Slot* slots, int64_t cap, const uint64_t* keys, int64_t n, in
   return inserted;
 }
 
+int64_t kv_rehash(const Slot* old_slots, int64_t old_cap, Slot* slots, int64_t cap,
+                  uint64_t home_base, uint64_t home_m, bool* full) {
+  const uint64_t mask = (uint64_t)cap - 1;
+  int lg = 0;
+  while ((1ll << lg) < cap) ++lg;
+  int64_t moved = 0;
+  for (int64_t i = 0; i < old_cap; ++i) {
+    const Slot& s = old_slots[i];
+    if (s.key == kEmptyKey) continue;
+    // the home slot for the NEW capacity (kv_table.hip home_slot), linear probing
+    uint64_t idx = (home_m ? ((s.key - home_base) * home_m) >> (64 - lg) : fmix64(s.key)) & mask;
+    bool placed = false;
+    for (uint64_t p = 0; p <= mask; ++p) {
+      if (slots[idx].key == kEmptyKey) {
+        slots[idx] = s;
+        placed = true;
+        break;
+      }
+      idx = (idx + 1) & mask;
+    }
+    if (placed) ++moved;
+    else if (full) *full = true;
+  }
+  return moved;
+}
+
 void kv_gather(const Slot* slots, const int64_t* idx, int64_t n, float* out, int field) {
   for (int64_t i = 0; i < n; ++i) {
     const int64_t s = idx[i];

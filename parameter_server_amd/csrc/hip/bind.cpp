@@ -20,6 +20,8 @@
 namespace psamd {
 // kv_table.hip
 void kv_init(void*, int64_t, hipStream_t);
+void kv_rehash(const void*, int64_t, void*, int64_t, uint64_t, uint64_t, unsigned long long*, int,
+               int32_t*, hipStream_t);
 void kv_resolve(void*, int64_t, const uint64_t*, int64_t, const int32_t*, int64_t*, float*, bool,
                 int, float, float, uint64_t, int32_t*, int32_t*, uint64_t, uint64_t, hipStream_t);
 void kv_accumulate_rows(void*, int64_t, const int64_t*, const float*, int64_t, const int32_t*, int,
@@ -1845,6 +1847,22 @@ PYBIND11_MODULE(_hipops, m) {
     psamd::kv_census(slots.data_ptr(), cap, ptr<unsigned long long>(out), cur_stream());
     return out;
   });
+  // growth: every occupied slot of `old_slots` into the larger, kv_init-ed `slots`;
+  // returns the device count of slots moved (a 0-dim int64 tensor)
+  m.def("kv_rehash", [](Tensor old_slots, Tensor slots, uint64_t home_base, uint64_t home_m,
+                        optional<Tensor> err) {
+    const int64_t old_cap = slot_capacity(old_slots), cap = slot_capacity(slots);
+    check(cap >= old_cap, "kv_rehash: the new table must not be smaller");
+    check(old_slots.device() == slots.device(), "kv_rehash: tables on different devices");
+    check(old_slots.data_ptr() != slots.data_ptr(), "kv_rehash: needs a new table");
+    auto moved = torch::zeros({psamd::kAccStripes * psamd::kAccStride},
+                              slots.options().dtype(at::kLong));
+    psamd::kv_rehash(old_slots.data_ptr(), old_cap, slots.data_ptr(), cap, home_base, home_m,
+                     ptr<unsigned long long>(moved), psamd::kAccStripes,
+                     optr<int32_t>(err, at::kInt, "err"), cur_stream());
+    return moved.sum();
+  }, py::arg("old_slots"), py::arg("slots"), py::arg("home_base") = 0, py::arg("home_m") = 0,
+     py::arg("err") = py::none());
 
   // ---------------- text parsing ----------------
   m.def("textparse_span", [] { return psamd::textparse_span(); });

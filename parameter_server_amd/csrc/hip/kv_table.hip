@@ -616,8 +616,66 @@ __global__ void kv_census_kernel(const Slot* __restrict__ slots, int64_t cap,
   }
 }
 
+// Growth: move every occupied slot of `old_slots` into the larger, freshly initialised
+// `slots` (kv_init ran in a launch of its own). The whole 32-byte record travels
+// unchanged; its new home is home_slot for the new capacity, claimed by CAS
+// kEmptyKey -> key with linear probing exactly as resolve_key inserts, so the new probe
+// chains have no gaps. Nothing reads the new table during the launch: the payload is a
+// plain store behind the claim. moved[] is a striped counter (acc_stripe layout, one
+// atomic per block); the launcher's caller sums it, so a growth needs no census.
+__global__ __launch_bounds__(256) void kv_rehash_kernel(
+    const Slot* __restrict__ old_slots, int64_t old_cap, Slot* __restrict__ slots, uint64_t mask,
+    uint64_t home_base, uint64_t home_m, int home_shr, unsigned long long* __restrict__ moved,
+    int stripes, int32_t* __restrict__ err) {
+  __shared__ int wcnt[4];
+  int cnt = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < old_cap;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const Slot s = old_slots[i];
+    if (s.key == kEmptyKey) continue;
+    uint64_t idx = home_slot(s.key, mask, home_base, home_m, home_shr) & mask;
+    bool placed = false;
+    for (uint64_t probe = 0; probe <= mask; ++probe) {
+      if (slots[idx].key == kEmptyKey &&
+          atomicCAS((unsigned long long*)&slots[idx].key, (unsigned long long)kEmptyKey,
+                    (unsigned long long)s.key) == kEmptyKey) {
+        Slot* d = &slots[idx];
+        d->w = s.w;
+        d->z = s.z;
+        d->n = s.n;
+        d->acc = s.acc;
+        d->cnt = s.cnt;
+        d->flags = s.flags;
+        placed = true;
+        break;
+      }
+      idx = (idx + 1) & mask;
+    }
+    if (placed) ++cnt;
+    else if (err) atomicOr(err, 1);  // new table exhausted (never when new cap >= old cap)
+  }
+  cnt = wave_sum(cnt);
+  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int tot = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    if (tot) atomicAdd(&moved[(int64_t)(blockIdx.x % stripes) * kAccStride], (unsigned long long)tot);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Host launchers
+void kv_rehash(const void* old_slots, int64_t old_cap, void* slots, int64_t cap,
+               uint64_t home_base, uint64_t home_m, unsigned long long* moved, int stripes,
+               int32_t* err, hipStream_t st) {
+  int lg = 0;
+  while ((1ll << lg) < cap) ++lg;
+  kv_rehash_kernel<<<grid_for(old_cap, 256), 256, 0, st>>>(
+      (const Slot*)old_slots, old_cap, (Slot*)slots, (uint64_t)(cap - 1), home_base, home_m,
+      64 - lg, moved, stripes, err);
+  PSAMD_HIP_CHECK(hipGetLastError());
+}
+
 void kv_init(void* slots, int64_t cap, hipStream_t st) {
   kv_init_kernel<<<grid_for(cap, 256, 8192), 256, 0, st>>>((Slot*)slots, cap);
   PSAMD_HIP_CHECK(hipGetLastError());

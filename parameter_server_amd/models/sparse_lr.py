@@ -49,6 +49,7 @@ from ..parallel.partition import KeyPartition
 from ..utils.trace import enabled as trace_enabled
 from ..utils.trace import trace_range
 from .sparse_lr_exact import ExactExchange
+from .sparse_lr_growth import TableGrowth
 from .sparse_lr_p2p import P2PExchange
 from .sparse_lr_padded import PaddedExchange
 
@@ -106,7 +107,14 @@ class SparseLRConfig:
     max_delta: float = 0.0               # per-update |dw| clip (trust region), 0 = off
     table_capacity: int = 0              # slots per shard (power of 2); 0 = auto
     table_load: float = 0.5              # auto capacity = num_features / G / load
-    max_table_bytes: int = 96 << 30      # cap for the auto size (per GPU)
+    max_table_bytes: int = 96 << 30      # cap for the auto size and for growth (per GPU)
+    # grow the table on the device instead of failing when it fills (sparse_lr_growth.py):
+    # once the host's upper bound of the occupied slots passes table_grow_check x capacity
+    # the exact count is taken, and a table more than table_grow_at full is rehashed into
+    # one at most table_grow_at / 2 full. Off: the capacity is fixed, as before
+    table_growth: bool = False
+    table_grow_check: float = 0.75
+    table_grow_at: float = 0.5
     init: InitRule = field(default_factory=InitRule)
     # ssp (lag >= 1) owner apply of the carried pushes: "post" = after the exchange's
     # pulls are resolved and the weights sent back (off the worker's critical path),
@@ -172,11 +180,12 @@ def algo_defaults(algo: str) -> dict:
     return dict(ALGO_DEFAULTS[algo.lower()])
 
 
-class SparseLRTrainer(PaddedExchange, ExactExchange, P2PExchange):
+class SparseLRTrainer(PaddedExchange, ExactExchange, P2PExchange, TableGrowth):
     """The trainer: construction, localisation, routing, ``step`` and the 1-GPU plans,
     reporting and checkpointing. The multi-GPU data planes are mixins: the padded and
     merged exchange (sparse_lr_padded.py), the exact / fused exchange and the generic
-    pull / push (sparse_lr_exact.py), the one-sided peer exchange (sparse_lr_p2p.py)."""
+    pull / push (sparse_lr_exact.py), the one-sided peer exchange (sparse_lr_p2p.py); so is
+    the opt-in table growth (sparse_lr_growth.py)."""
 
     def __init__(self, cfg: SparseLRConfig, comm: Comm | None = None, device="cpu"):
         # (checked before anything is allocated: the table may be most of the HBM)
@@ -189,6 +198,7 @@ class SparseLRTrainer(PaddedExchange, ExactExchange, P2PExchange):
         self.cfg = cfg
         self.comm = comm or LocalComm(device)
         self.G, self.rank = self.comm.world, self.comm.rank
+        self._growth_supported(cfg, self.G)
         self.device = torch.device(device)
         self.gpu = self.device.type == "cuda"
         self.bits = key_bits_for(cfg.num_features)
@@ -308,6 +318,7 @@ class SparseLRTrainer(PaddedExchange, ExactExchange, P2PExchange):
         # FixingFloat pushes: the stochastic-rounding seed (the device step clock varies it)
         self._ff_seed = (cfg.seed * 7919 + 17) & ((1 << 64) - 1)
         self._plans = {}  # 1 GPU: native launch lists of the fused step (_step_plan)
+        self._growth_setup()
         self.step_count = 0
         self.examples = 0
         self.comm_bytes = 0
@@ -328,6 +339,8 @@ class SparseLRTrainer(PaddedExchange, ExactExchange, P2PExchange):
         done = 0
         while done < count:
             n = min(chunk, count - done)
+            if self._growth is not None:
+                self._growth.admit(n)
             mk = random_keys_in_range(lo, hi, n, g, self.device)
             self.table.resolve(mk, insert=True, with_w=False)
             done += n
@@ -370,6 +383,8 @@ class SparseLRTrainer(PaddedExchange, ExactExchange, P2PExchange):
         pull runs in this step's update launch (after the update, in the same
         workgroups), and the next ``step(loc=next_loc)`` skips its own pull. The table
         is fully updated when this step's work completes either way."""
+        if self._growth is not None:  # (before anything of this step is issued)
+            self._growth_step(keys, loc, next_loc)
         pre, self._pre = self._pre, None  # a pull issued ahead serves the next step only
         if self.localize_mode == "tpf" and self.G == 1:
             B = labels.numel()
@@ -866,6 +881,8 @@ class SparseLRTrainer(PaddedExchange, ExactExchange, P2PExchange):
             "nnz_w": float(m[8]),
             "updt_ratio": math.sqrt(float(m[10])) / math.sqrt(max(float(m[9]), 1e-20)),
         }
+        out["table_capacity"] = self.table.capacity
+        out["table_grown"] = self._growth.grown if self._growth is not None else 0
         if reset:
             self.metrics.zero_()
             self.stats.view(-1, 16)[:, 1:].zero_()  # keep the cumulative nnz column
@@ -907,9 +924,11 @@ class SparseLRTrainer(PaddedExchange, ExactExchange, P2PExchange):
     def load_state_dict(self, sd: dict):
         from ..ops.keymix import mix
 
-        self._pre = None  # the table changes under any pull issued ahead
         keys = mix(sd["keys"].to(self.device), self.bits)
         own = self.part.owner_of(keys) == self.rank
+        # growth on: room for this rank's keys first (collective when G > 1)
+        self._growth_load(own)
+        self._table_changed()  # the table changes under any pull issued ahead
         self.table.load(keys[own], sd["w"].to(self.device)[own], sd["z"].to(self.device)[own],
                         sd["n"].to(self.device)[own])
         self.step_count = int(sd.get("step", 0))

@@ -35,6 +35,8 @@ class PaddedExchange:
             return
         if not self.padded:
             raise NotImplementedError("key-less steps need the padded exchange")
+        if self._growth is not None:  # (this owner still receives its peers' keys)
+            self._growth_step(None, None, None)
         if self.merged:
             return self._mx_step(None, None, idle=True)
         for _, fn in self.step_segments(None, None, idle=True):

@@ -193,5 +193,47 @@ class KVTable:
         self.check_ok()
         return slot
 
+    # ---------------------------------------------------------------- growth
+    def grow(self, capacity: int) -> int:
+        """Rehash every occupied slot, as the whole 32-byte record, into a table of
+        ``capacity`` slots (rounded up to a power of two), in place: this object stays,
+        ``slots`` and ``capacity`` are replaced. Returns the occupied count (also left
+        in ``num_inserted``). The error word, the init rule and the home mapping carry
+        over. Slot indices and launch lists taken before the call are stale after it."""
+        cap = next_pow2(max(64, int(capacity)))
+        if cap < self.capacity:
+            raise ValueError(f"KVTable.grow: capacity {cap} is below the current {self.capacity}")
+        if cap == self.capacity:
+            self.num_inserted = self.census()[0]
+            return self.num_inserted
+        old = self.slots
+        new = torch.empty((cap, 4), dtype=torch.int64, device=self.device)
+        if self.gpu:
+            hipops().kv_init(new)
+            moved = hipops().kv_rehash(old, new, self.home_base, self.home_m, self._err)
+            # the caching allocator hands the old block out again only to work queued
+            # behind the rehash on this stream
+            old.record_stream(torch.cuda.current_stream(self.device))
+            moved = int(moved.item())
+        else:
+            core().kv_init(ptr(new), cap)
+            moved, full = core().kv_rehash(ptr(old), self.capacity, ptr(new), cap,
+                                           self.home_base, self.home_m)
+            if full:
+                raise RuntimeError("KVTable full: increase capacity")
+        self.slots, self.capacity = new, cap
+        self.num_inserted = int(moved)
+        return self.num_inserted
+
+    def remap_slots(self, old_slots: torch.Tensor, slot_idx: torch.Tensor) -> torch.Tensor:
+        """Slot indices into ``old_slots`` (this table's slots before a ``grow``) as the
+        indices of the same keys in the table now; -1 (absent) stays -1."""
+        cap = old_slots.shape[0]
+        ok = (slot_idx >= 0) & (slot_idx < cap)
+        keys = old_slots[:, 0][slot_idx.clamp(0, cap - 1)]
+        ok &= keys != EMPTY_KEY
+        new, _ = self.resolve(keys.contiguous(), insert=False, with_w=False)
+        return torch.where(ok, new, torch.full_like(new, -1))
+
     def nbytes(self) -> int:
         return self.capacity * 32
