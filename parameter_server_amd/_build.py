@@ -3,9 +3,12 @@
 Builds two shared objects next to this file (so they travel with the repo
 snapshot to a GPU box and are visibly loaded from the tree):
 
-* ``_hipops.so``  -- hand-written HIP kernels for gfx950 (``csrc/hip/*.hip``)
-  plus their torch/pybind11 bindings (``csrc/hip/bind.cpp``). Compiled directly
-  with ``hipcc --offload-arch=gfx950`` (no hipify step, no CUDA sources).
+* ``_hipops.so``  -- hand-written HIP kernels for gfx950 (``csrc/hip/*.hip``,
+  each with an ``X.h`` that declares its host launchers) plus their
+  torch/pybind11 bindings, one unit per kernel family (``csrc/hip/bind*.cpp``:
+  ``bind.cpp`` holds the module and the dense unit, ``bind_common.h`` what the
+  units share). Compiled directly with ``hipcc --offload-arch=gfx950`` (no
+  hipify step, no CUDA sources) and linked into the one shared object.
 * ``_pscore.so``  -- the host C++ runtime (``csrc/core/*.cc``): TCP van,
   protobuf-text config parser, data parsers, RecordIO, crc32c/murmur3,
   CountMin/Bloom/Bitmap, CPU reference kernels. Pure C++17 + pybind11; it does
@@ -79,15 +82,17 @@ def build_hipops(jobs: int = 8, verbose: bool = False) -> Path:
         objs.append(obj)
         if _stale(obj, src, headers):
             jobs_list.append([HIPCC, *common, "-c", str(src), "-o", str(obj)])
-    bind = src_dir / "bind.cpp"
-    bobj = out_dir / "bind.o"
-    objs.append(bobj)
-    if _stale(bobj, bind, headers):
-        tflags = [f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-DTORCH_EXTENSION_NAME=_hipops",
-                  "-DTORCH_API_INCLUDE_EXTENSION_H", "-DUSE_ROCM=1", "-D__HIP_PLATFORM_AMD__=1"]
-        incs = sum((["-isystem", p] for p in inc + _py_includes()), [])
-        jobs_list.append([HIPCC, *common, *tflags, *incs, "-x", "hip", "-c", str(bind),
-                          "-o", str(bobj)])
+    tflags = [f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-DTORCH_EXTENSION_NAME=_hipops",
+              "-DTORCH_API_INCLUDE_EXTENSION_H", "-DUSE_ROCM=1", "-D__HIP_PLATFORM_AMD__=1"]
+    incs = sum((["-isystem", p] for p in inc + _py_includes()), [])
+    # (the binding units first: each spends most of its time in the torch headers, so
+    # they are the long jobs of the pool)
+    for bind in sorted(src_dir.glob("bind*.cpp")):
+        bobj = out_dir / (bind.stem + ".o")
+        objs.append(bobj)
+        if _stale(bobj, bind, headers):
+            jobs_list.insert(0, [HIPCC, *common, *tflags, *incs, "-x", "hip", "-c", str(bind),
+                                 "-o", str(bobj)])
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         futs = [ex.submit(_run, c) for c in jobs_list]
         for c, f in zip(jobs_list, futs):

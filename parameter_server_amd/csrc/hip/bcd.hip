@@ -22,6 +22,7 @@
 //    columns use atomics -> no per-column wave imbalance for power-law columns.
 //  * every rank applies the (deterministic) server update to a replicated copy
 //    of the block after an all-reduce of (G, U); there is no pull phase.
+#include "bcd.h"
 #include "common.cuh"
 
 #include <algorithm>

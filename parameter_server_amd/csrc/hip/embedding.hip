@@ -18,6 +18,7 @@
 //   colred_bf16      column reductions: dw = h^T coef, the last hidden layer's bias
 //                    gradient, plain column sums (library-GEMM backend)
 //   adam_update      fp32 master weights + bf16 copy for the GEMMs
+#include "embedding.h"
 #include "common.cuh"
 #include "kv_slot.cuh"
 
@@ -901,9 +902,6 @@ void emb_update(const int64_t* slot, int64_t n, const int32_t* n_dev, int64_t ca
   }
   PSAMD_HIP_CHECK(hipGetLastError());
 }
-
-void colred_bf16(const void* x, int64_t B, int N, const float* s, float* out, const float* g,
-                 float* out_pos, hipStream_t st);
 
 void wd_head(const void* h, int64_t B, int H, const float* w, const float* b, const float* wide_w,
              int64_t wide_cap, const int32_t* local_col, int S, const float* labels,

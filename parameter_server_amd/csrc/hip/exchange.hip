@@ -21,6 +21,7 @@
 // off[G+1] (device) are the owner run offsets. Keys past C in a run are dropped
 // and counted in *ovf (the trainer raises on it; the capacity carries a large
 // statistical margin over the per-peer count of hashed keys).
+#include "exchange.h"
 #include "common.cuh"
 #include "loss.cuh"
 
@@ -157,13 +158,11 @@ void xchg_pack_keys(const uint64_t* ukeys, const int32_t* n_uniq, int64_t n_host
 
 void xchg_pack_grads(const float* grad, const int32_t* perm, const int32_t* n_uniq,
                      int64_t n_host, const int64_t* off, int G, int64_t C, int kw, int64_t H,
-                     int32_t* send, uint32_t* hist, int hist_stripes, double* metrics,
-                     int64_t* step_counter, const int32_t* ovf, int32_t* ovf_host,
+                     int32_t* send, const AucOut& auc, const int32_t* ovf, int32_t* ovf_host,
                      hipStream_t st) {
-  xchg_pack_grads_kernel<<<grid_for(n_host, 256), 256, 0, st>>>(grad, perm, n_uniq, n_host, off,
-                                                                 G, C, kw, H, send, hist, hist_stripes,
-                                                                 metrics, step_counter, ovf,
-                                                                 ovf_host);
+  xchg_pack_grads_kernel<<<grid_for(n_host, 256), 256, 0, st>>>(
+      grad, perm, n_uniq, n_host, off, G, C, kw, H, send, auc.hist, auc.stripes, auc.metrics,
+      auc.step_counter, ovf, ovf_host);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
@@ -339,12 +338,8 @@ void xchg_ff_pack_grads(const float* grad, const int32_t* perm, const int32_t* n
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
-// the two halves of xchg_ff_pack_grads around a producer that stages the rows itself (the
-// flat layout's tpf_pack_grads writes gstage and the rows' min / max)
-void xchg_ff_init(int32_t* send, int G, int64_t H, hipStream_t st) {
-  xchg_ff_init_kernel<<<1, 64, 0, st>>>(send, G, H);
-  PSAMD_HIP_CHECK(hipGetLastError());
-}
+// the encode half of xchg_ff_pack_grads after a producer that stages the rows itself (the
+// flat layout's tpf_pack_grads writes gstage and its workgroups' min / max partials)
 void xchg_ff_encode(const float* gstage, int G, int64_t C, int kw, int64_t H, int nb, uint64_t seed,
                     const int64_t* step, int32_t* send, int per, hipStream_t st) {
   dim3 grid(grid_for(C, 256, 512), G);

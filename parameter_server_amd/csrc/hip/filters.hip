@@ -15,6 +15,7 @@
 // Key signature (reference KeyCachingFilter: crc32c of the first <= 2048 key
 // bytes, src/filter/key_caching.h:18,43): a whole-array, position-dependent
 // 64-bit hash computed on device so the key list never leaves HBM.
+#include "filters.h"
 #include "common.cuh"
 #include "countmin.cuh"
 #include <stdexcept>

@@ -14,6 +14,7 @@
 // build s_f and q_f = sum x^2 v^2; the wide margin is a 64-lane reduction. Outputs:
 // coef[b] = p (for the wide-weight gradient), dX0[b*S+i, f] = p (x_i s_f - x_i^2 v_if)
 // (bf16, reduced per unique key by emb_grad_reduce), loss / accuracy / AUC histogram.
+#include "fm.h"
 #include "common.cuh"
 
 #include <algorithm>

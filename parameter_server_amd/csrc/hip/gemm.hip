@@ -25,6 +25,7 @@
 // bf16 tensor (backward through an activation), bf16 and/or fp32 stores, and the
 // output's column sums (the input-gradient GEMM of layer i emits dZ of layer i-1,
 // whose column sums are that layer's bias gradient: no second pass over dZ).
+#include "gemm.h"
 #include "common.cuh"
 
 #include <hip/hip_bf16.h>

@@ -24,6 +24,7 @@
 // Requirements (checked by the binding): K % 64 == 0, lda / ldb multiples of 8
 // (16-B rows), 16-B aligned operands. Rows past M / N are clamped on load and
 // masked on store.
+#include "gemm256.h"
 #include "common.cuh"
 
 #include <hip/hip_bf16.h>

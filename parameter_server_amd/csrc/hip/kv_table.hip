@@ -16,6 +16,7 @@
 // dedupe keys per launch); cross-source duplicates are applied by sequential
 // launches (reference semantics: every push message is one optimizer step)
 // or by the accumulate/apply pair (synchronous / BSP aggregation).
+#include "kv_table.h"
 #include "kv_slot.cuh"
 #include "loss.cuh"
 #include <stdexcept>
@@ -665,14 +666,13 @@ __global__ __launch_bounds__(256) void kv_rehash_kernel(
 
 // ---------------------------------------------------------------------------
 // Host launchers
-void kv_rehash(const void* old_slots, int64_t old_cap, void* slots, int64_t cap,
-               uint64_t home_base, uint64_t home_m, unsigned long long* moved, int stripes,
-               int32_t* err, hipStream_t st) {
+void kv_rehash(const void* old_slots, int64_t old_cap, const TableRef& t,
+               unsigned long long* moved, int stripes, int32_t* err, hipStream_t st) {
   int lg = 0;
-  while ((1ll << lg) < cap) ++lg;
+  while ((1ll << lg) < t.cap) ++lg;
   kv_rehash_kernel<<<grid_for(old_cap, 256), 256, 0, st>>>(
-      (const Slot*)old_slots, old_cap, (Slot*)slots, (uint64_t)(cap - 1), home_base, home_m,
-      64 - lg, moved, stripes, err);
+      (const Slot*)old_slots, old_cap, (Slot*)t.slots, (uint64_t)(t.cap - 1), t.home_base,
+      t.home_m, 64 - lg, moved, stripes, err);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
@@ -681,31 +681,29 @@ void kv_init(void* slots, int64_t cap, hipStream_t st) {
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
-void kv_resolve(void* slots, int64_t cap, const uint64_t* keys, int64_t n, const int32_t* n_dev,
-                int64_t* out_slot, float* out_w, bool insert, int init_type, float init_v,
-                float init_s, uint64_t seed, int32_t* err, int32_t* inserted, uint64_t home_base,
-                uint64_t home_m, hipStream_t st) {
+void kv_resolve(const TableRef& t, const uint64_t* keys, int64_t n, const int32_t* n_dev,
+                int64_t* out_slot, float* out_w, bool insert, const KeyInit& init, int32_t* err,
+                int32_t* inserted, hipStream_t st) {
   int lg = 0;
-  while ((1ll << lg) < cap) ++lg;
+  while ((1ll << lg) < t.cap) ++lg;
   kv_resolve_kernel<<<grid_for(n, 256), 256, 0, st>>>(
-      (Slot*)slots, (uint64_t)(cap - 1), home_base, home_m, 64 - lg, keys, n, n_dev, out_slot,
-      out_w, insert ? 1 : 0, init_type, init_v, init_s, seed, err, inserted);
+      (Slot*)t.slots, (uint64_t)(t.cap - 1), t.home_base, t.home_m, 64 - lg, keys, n, n_dev,
+      out_slot, out_w, insert ? 1 : 0, init.type, init.v, init.s, init.seed, err, inserted);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
-void kv_resolve_rows(void* slots, int64_t cap, const int32_t* recv, int G, int64_t H, int64_t C,
-                     int kw, int64_t* out_slot, float* out_w, int64_t wstride, bool insert,
-                     int init_type, float init_v, float init_s, uint64_t seed, int32_t* err,
-                     int32_t* inserted, uint64_t home_base, uint64_t home_m, uint64_t* out_key,
+void kv_resolve_rows(const TableRef& t, const int32_t* recv, int G, int64_t H, int64_t C, int kw,
+                     int64_t* out_slot, float* out_w, int64_t wstride, bool insert,
+                     const KeyInit& init, int32_t* err, int32_t* inserted, uint64_t* out_key,
                      int32_t* bnd, int lgP, hipStream_t st) {
   int lg = 0;
-  while ((1ll << lg) < cap) ++lg;
+  while ((1ll << lg) < t.cap) ++lg;
   dim3 grid(grid_for(C, 256, 1024), G);
-  if (bnd && !home_m) throw std::runtime_error("kv_resolve_rows: partition bounds need an ordered home");
+  if (bnd && !t.home_m) throw std::runtime_error("kv_resolve_rows: partition bounds need an ordered home");
   kv_resolve_rows_kernel<<<grid, 256, 0, st>>>(
-      (Slot*)slots, (uint64_t)(cap - 1), home_base, home_m, 64 - lg, recv, H, C, kw, out_slot,
-      out_w, wstride > 0 ? wstride : C, insert ? 1 : 0, init_type, init_v, init_s, seed, err,
-      inserted, out_key, bnd, lgP);
+      (Slot*)t.slots, (uint64_t)(t.cap - 1), t.home_base, t.home_m, 64 - lg, recv, H, C, kw,
+      out_slot, out_w, wstride > 0 ? wstride : C, insert ? 1 : 0, init.type, init.v, init.s,
+      init.seed, err, inserted, out_key, bnd, lgP);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
@@ -723,15 +721,13 @@ void kv_set(void* slots, int64_t cap, const int64_t* slot_idx, int64_t n, const 
 }
 
 void kv_update(void* slots, int64_t cap, const int64_t* slot_idx, const float* grad, int64_t n,
-               const int32_t* n_dev, int algo, int lr_type, float alpha, float beta, float l1,
-               float l2, float grad_scale, float max_delta, double* stats, int acc_stripes,
-               uint32_t* hist, int nbins, int hist_stripes, double* metrics,
-               int64_t* step_counter, hipStream_t st) {
-  UpdateParams p{algo, lr_type, alpha, beta, l1, l2, grad_scale, max_delta};
-  if (hist && nbins != 2048) throw std::runtime_error("kv_update: the fused AUC needs 2048 bins");
-  kv_update_kernel<<<grid_for(n, 256), 256, 0, st>>>((Slot*)slots, cap, slot_idx, grad, n, n_dev,
-                                                     p, stats, acc_stripes, hist, nbins,
-                                                     hist_stripes, metrics, step_counter);
+               const int32_t* n_dev, const UpdateParams& p, const StripedAcc& stats,
+               const AucOut& auc, hipStream_t st) {
+  if (auc.hist && auc.nbins != 2048)
+    throw std::runtime_error("kv_update: the fused AUC needs 2048 bins");
+  kv_update_kernel<<<grid_for(n, 256), 256, 0, st>>>(
+      (Slot*)slots, cap, slot_idx, grad, n, n_dev, p, stats.ptr, stats.stripes, auc.hist,
+      auc.nbins, auc.stripes, auc.metrics, auc.step_counter);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
@@ -753,27 +749,22 @@ void kv_accumulate_rows(void* slots, int64_t cap, const int64_t* slot_idx, const
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
-void kv_apply_accumulated(void* slots, int64_t cap, const int64_t* touched, const int32_t* n_touched,
-                          int64_t max_n, int algo, int lr_type, float alpha, float beta, float l1,
-                          float l2, float grad_scale, float max_delta, double* stats, int acc_stripes,
-                          hipStream_t st) {
-  UpdateParams p{algo, lr_type, alpha, beta, l1, l2, grad_scale, max_delta};
-  kv_apply_accumulated_kernel<<<grid_for(max_n, 256), 256, 0, st>>>((Slot*)slots, cap, touched,
-                                                                    n_touched, max_n, p, stats,
-                                                                    acc_stripes);
+void kv_apply_accumulated(void* slots, int64_t cap, const int64_t* touched,
+                          const int32_t* n_touched, int64_t max_n, const UpdateParams& p,
+                          const StripedAcc& stats, hipStream_t st) {
+  kv_apply_accumulated_kernel<<<grid_for(max_n, 256), 256, 0, st>>>(
+      (Slot*)slots, cap, touched, n_touched, max_n, p, stats.ptr, stats.stripes);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
 void kv_update_rows(void* slots, int64_t cap, const int64_t* slot_idx, const float* grad,
                     int64_t gstride, const int32_t* recv, int G, int64_t H, int64_t C,
-                    unsigned long long* link, int64_t link_size, int32_t* nxt, int algo,
-                    int lr_type, float alpha, float beta, float l1, float l2, float grad_scale,
-                    float max_delta, double* stats, int acc_stripes, hipStream_t st) {
+                    unsigned long long* link, int64_t link_size, int32_t* nxt,
+                    const UpdateParams& p, const StripedAcc& stats, hipStream_t st) {
   if (cap > (int64_t(1) << 32)) throw std::runtime_error("kv_update_rows: capacity > 2^32");
   if (link_size < 2 * (int64_t)G * C || (link_size & (link_size - 1)))
     throw std::runtime_error("kv_update_rows: link scratch must be a power of two >= 2*G*C");
   if (G < 1 || G > kMaxChain) throw std::runtime_error("kv_update_rows: 1..64 source rows");
-  UpdateParams p{algo, lr_type, alpha, beta, l1, l2, grad_scale, max_delta};
   fill_async<unsigned long long>(link, link_size, ~0ull, st);
   dim3 grid(grid_for(C, 256, 1024), G);
   kv_link_rows_kernel<<<grid, 256, 0, st>>>(slot_idx, cap, grad, gstride, recv, H, C, link,
@@ -781,23 +772,21 @@ void kv_update_rows(void* slots, int64_t cap, const int64_t* slot_idx, const flo
   PSAMD_HIP_CHECK(hipGetLastError());
   kv_apply_rows_kernel<<<grid, 256, 0, st>>>((Slot*)slots, cap, slot_idx, grad, gstride, recv, H,
                                              C, link, (uint64_t)(link_size - 1), nxt,
-                                             (int64_t)G * C, p, stats, acc_stripes);
+                                             (int64_t)G * C, p, stats.ptr, stats.stripes);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
 void kv_apply_part(void* slots, int64_t cap, const int64_t* slot_idx, const uint64_t* keys,
                    const float* grad, int64_t gstride, const int32_t* recv, int G, int64_t H,
-                   int64_t C, const int32_t* bnd, int lgP, int algo, int lr_type, float alpha,
-                   float beta, float l1, float l2, float grad_scale, float max_delta,
-                   double* stats, int acc_stripes, int ffnb, int kw, hipStream_t st) {
+                   int64_t C, const int32_t* bnd, int lgP, const UpdateParams& p,
+                   const StripedAcc& stats, int ffnb, int kw, hipStream_t st) {
   if (cap > (int64_t(1) << 32) - 1) throw std::runtime_error("kv_apply_part: capacity >= 2^32");
   if ((int64_t)G * C >= (int64_t(1) << 31)) throw std::runtime_error("kv_apply_part: G*C >= 2^31");
   if (G < 1 || G > kMaxChain) throw std::runtime_error("kv_apply_part: 1..64 source rows");
   if (lgP < 0 || lgP > 20) throw std::runtime_error("kv_apply_part: lgP in 0..20");
-  UpdateParams p{algo, lr_type, alpha, beta, l1, l2, grad_scale, max_delta};
   kv_apply_part_kernel<<<1 << lgP, 256, 0, st>>>((Slot*)slots, cap, slot_idx, keys, grad, gstride,
-                                                 recv, H, C, G, bnd, lgP, p, stats, acc_stripes,
-                                                 ffnb, kw);
+                                                 recv, H, C, G, bnd, lgP, p, stats.ptr,
+                                                 stats.stripes, ffnb, kw);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 

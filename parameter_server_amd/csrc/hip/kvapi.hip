@@ -14,6 +14,7 @@
 // src/filter/key_caching.h:6-76) push key-less rows [hdr 4 | values C*k] (kw = 0)
 // against the owner's cached slots, and their pulls need no request rows at all: the
 // owner serves its cached slots straight into the one value all-to-all.
+#include "kvapi.h"
 #include "common.cuh"
 
 namespace psamd {

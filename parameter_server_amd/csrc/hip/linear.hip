@@ -13,6 +13,7 @@
 // reference alterStorage sparse_matrix.h:186-241, is ever materialised) and
 // does a 64-lane segmented scan; only segments that cross a wave boundary
 // issue one float atomic per wave piece.
+#include "linear.h"
 #include "common.cuh"
 #include "loss.cuh"
 #include <stdexcept>
@@ -391,9 +392,9 @@ void linear_bwd(const int32_t* pos_s, const int32_t* segid, int64_t n, const int
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
-void auc_from_hist(uint32_t* hist, int nbins, int hist_stripes, double* metrics,
-                   int64_t* step_counter, hipStream_t st) {
-  auc_from_hist_kernel<<<1, 256, 0, st>>>(hist, nbins, hist_stripes, metrics, step_counter);
+void auc_from_hist(const AucOut& auc, hipStream_t st) {
+  auc_from_hist_kernel<<<1, 256, 0, st>>>(auc.hist, auc.nbins, auc.stripes, auc.metrics,
+                                          auc.step_counter);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 

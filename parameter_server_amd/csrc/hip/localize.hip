@@ -13,6 +13,8 @@
 //              segment starts, per-nnz local column, per-sorted-element segment
 //   4. split:  owner boundaries by binary search (K14, sliceKeyOrderedMsg,
 //              src/system/message.h:120-159)
+#include "localize.h"
+#include "primitives.h"
 #include "common.cuh"
 #include <stdexcept>
 #include <string>
@@ -145,10 +147,6 @@ void mix_keys(const uint64_t* keys, int64_t n, KeyMix m, uint64_t* h, bool inver
   mix_kernel<<<grid_for(n, 256), 256, 0, st>>>(keys, n, m, h, inverse ? 1 : 0);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
-
-size_t scan_i32_temp_bytes(int64_t n);
-void scan_i32(const int32_t* in, int32_t* out, int64_t n, void* temp, bool inclusive,
-              hipStream_t st);
 
 size_t scan_temp_bytes(int64_t n) { return scan_i32_temp_bytes(n); }
 

@@ -28,6 +28,7 @@
 //   mt_scan_kernel   VGPRs 40, SGPRs 36, ScratchSize 0, LDS    68 B, occupancy 8
 //   mt_emit_kernel   VGPRs 55, SGPRs 54, ScratchSize 0, LDS 37924 B, occupancy 4 (LDS: four
 //                    workgroups of four waves a CU)
+#include "modeltext.h"
 #include "common.cuh"
 #include "../core/textfmt.h"
 

@@ -35,6 +35,7 @@
 // and reports through err (bit 8) instead of hanging; the post's last kernel publishes
 // err into pinned host memory, so the trainer fails at the first push that gave up
 // (its sequence number is consumed: the owner would wait for it forever).
+#include "p2p.h"
 #include "kv_slot.cuh"
 
 #include <hip/hip_runtime.h>
@@ -220,14 +221,13 @@ static void p2p_check_g(int G, int self) {
 }
 
 void p2p_lookup_rows(const void* tabs, int G, int self, const int32_t* send, int64_t H,
-                     int64_t C, int kw, float* wout, int64_t* slot_out, int init_type,
-                     float init_v, float init_s, uint64_t seed, int32_t* err, int32_t* inserted,
-                     hipStream_t st) {
+                     int64_t C, int kw, float* wout, int64_t* slot_out, const KeyInit& init,
+                     int32_t* err, int32_t* inserted, hipStream_t st) {
   p2p_check_g(G, self);
   dim3 grid(grid_for(C, 256, 1024), G);
   p2p_lookup_rows_kernel<<<grid, 256, 0, st>>>((const PeerTab*)tabs, self, send, H, C, kw, wout,
-                                               slot_out, init_type, init_v, init_s, seed, err,
-                                               inserted);
+                                               slot_out, init.type, init.v, init.s, init.seed,
+                                               err, inserted);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 

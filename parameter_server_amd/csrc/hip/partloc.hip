@@ -27,6 +27,7 @@
 // averages <= HCAP / 1.6 occurrences, which bounds its distinct keys even when
 // every key is distinct. A bucket whose distinct keys overflow the LDS hash sets
 // *err (the caller raises); the output is then incomplete.
+#include "partloc.h"
 #include "common.cuh"
 
 #include <stdexcept>

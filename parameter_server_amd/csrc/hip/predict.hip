@@ -21,6 +21,7 @@
 // to the table and has no error word. For given inputs (table bytes included) a margin is
 // the same bits on every run: a lane sums its occurrences in index order and the group
 // reduces in a fixed xor tree.
+#include "predict.h"
 #include "kv_slot.cuh"
 #include "loss.cuh"
 #include <stdexcept>
@@ -176,21 +177,21 @@ static void predict_launch(const void* slots, int64_t cap, uint64_t home_base, u
 // (~75 occurrences) and longer
 static int predict_lanes(int64_t nnz, int64_t B) { return B > 0 && nnz / B >= 64 ? 64 : 8; }
 
-void predict_rows(const void* slots, int64_t cap, uint64_t home_base, uint64_t home_m, KeyMix km,
-                  const uint64_t* keys, int64_t nnz, const int64_t* row_ptr, int width,
-                  const float* vals, const float* labels, int64_t B, int loss_type, float* margin,
-                  double* metrics, int acc_stripes, unsigned long long* hist, int nbins,
-                  int hist_stripes, int lanes, hipStream_t st) {
+void predict_rows(const TableRef& t, KeyMix km, const uint64_t* keys, int64_t nnz,
+                  const int64_t* row_ptr, int width, const float* vals, const float* labels,
+                  int64_t B, int loss_type, float* margin, const StripedAcc& metrics,
+                  unsigned long long* hist, int nbins, int hist_stripes, int lanes,
+                  hipStream_t st) {
   if (B <= 0) return;
   if (lanes == 0) lanes = predict_lanes(nnz, B);
   if (lanes == 64)
-    predict_launch<64, 2>(slots, cap, home_base, home_m, km, keys, nnz, row_ptr, width, vals,
-                          labels, B, loss_type, margin, metrics, acc_stripes, hist, nbins,
-                          hist_stripes, st);
+    predict_launch<64, 2>(t.slots, t.cap, t.home_base, t.home_m, km, keys, nnz, row_ptr, width,
+                          vals, labels, B, loss_type, margin, metrics.ptr, metrics.stripes, hist,
+                          nbins, hist_stripes, st);
   else if (lanes == 8)
-    predict_launch<8, 5>(slots, cap, home_base, home_m, km, keys, nnz, row_ptr, width, vals,
-                         labels, B, loss_type, margin, metrics, acc_stripes, hist, nbins,
-                         hist_stripes, st);
+    predict_launch<8, 5>(t.slots, t.cap, t.home_base, t.home_m, km, keys, nnz, row_ptr, width,
+                         vals, labels, B, loss_type, margin, metrics.ptr, metrics.stripes, hist,
+                         nbins, hist_stripes, st);
   else
     throw std::invalid_argument("predict_rows: lanes per row must be 0 (auto), 8 or 64");
 }

@@ -15,6 +15,7 @@
 //                     scan over them; the tile is reordered in LDS and written out
 //                     digit-run contiguous (coalesced stores).
 // Every global index is bounds-checked.
+#include "primitives.h"
 #include "common.cuh"
 #include <stdexcept>
 #include <string>

@@ -18,6 +18,7 @@
 // decoupled look-back (1 global-histogram kernel + 3 scatter passes) were correct
 // but 7.9 ms vs 0.2 ms: with ~600 tiles resident at once every tile walks the
 // predecessors' published counts serially; the reduce-then-scan passes stay.
+#include "sort32.h"
 #include "common.cuh"
 
 #include <algorithm>

@@ -16,6 +16,7 @@
 // Index type int32 (localized, the common case — reference CHECKs localize
 // happened before times) or int64; value type float or double; binary matrices
 // pass val == nullptr (implicit 1). y = alpha * (A x) + beta * y.
+#include "spmv.h"
 #include "common.cuh"
 
 namespace psamd {

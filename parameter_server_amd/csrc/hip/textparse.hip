@@ -33,6 +33,7 @@
 // '\n'), every output size comes from the counting pass and is checked against the
 // capacities before anything is emitted (sticky H_CAP), every emitted index is guarded,
 // and every loop over a token is bounded by textnum::kMaxTok + 1.
+#include "textparse.h"
 #include "common.cuh"
 #include "../core/textnum.h"
 

@@ -27,6 +27,7 @@
 //
 // Buckets are ranges of the mixed key space, so the unique keys come out sorted
 // (the multi-GPU owner split and the ordered home slots of the KV table rely on it).
+#include "tploc.h"
 #include "countmin.cuh"
 #include "kv_slot.cuh"
 #include "loss.cuh"
@@ -2557,9 +2558,9 @@ tpf_unpack_w_kernel(const int32_t* __restrict__ cnt, const int32_t* __restrict__
 }
 
 // every key's gradient (its entries' partials summed in LDS, 64-bit fixed point as in
-// tpf_step) into its owner's row; ff = 1: f32 into gstage[p * C + i] and the row's
-// FixingFloat min / max (header words 2 / 3, order-preserving ints; xchg_ff_init ran
-// first) for xchg_ff_encode. The owner's last bucket writes the row's gradient count.
+// tpf_step) into its owner's row; ff = 1: f32 into gstage[p * C + i] and the
+// workgroup's FixingFloat min / max partial behind the rows (gstage[G * C + 2 b]), which
+// xchg_ff_encode reduces per row. The owner's last bucket writes the row's gradient count.
 // Block 0: the step's AUC epilogue and the overflow flag to the host.
 __device__ __forceinline__ int tpf_ff_ord(float f) {
   const int b = __float_as_int(f);
@@ -2904,15 +2905,15 @@ void tpf_unpack_w(int64_t n, int bits, int G, const int32_t* cnt, const int32_t*
 
 void tpf_pack_grads(int64_t n, int bits, int G, const int32_t* cnt, const int32_t* ent_pos,
                     const uint16_t* ent_j, int64_t C, int kw, int64_t H, const float* psum,
-                    int64_t p_cap, int32_t* send, bool ff, float* gstage, uint32_t* hist,
-                    int hist_stripes, double* metrics, int64_t* step_counter, const int32_t* ovf,
-                    int32_t* ovf_host, hipStream_t st) {
+                    int64_t p_cap, int32_t* send, bool ff, float* gstage, const AucOut& auc,
+                    const int32_t* ovf, int32_t* ovf_host, hipStream_t st) {
   const int per = tpf_per_owner(n, bits, G);
   // (+1 workgroup: the AUC epilogue / overflow publication, off unit 0's critical path)
   const int groups = tpf_groups(n, bits);
-  tpf_pack_grads_kernel<<<(unsigned)groups + ((hist || ovf_host) ? 1u : 0u), tpf::kThr, 0, st>>>(
-      cnt, ent_pos, ent_j, per, C, kw, H, psum, p_cap, send, ff ? 1 : 0, gstage, hist,
-      hist_stripes, metrics, step_counter, ovf, ovf_host, groups);
+  tpf_pack_grads_kernel<<<(unsigned)groups + ((auc.hist || ovf_host) ? 1u : 0u), tpf::kThr, 0,
+                          st>>>(cnt, ent_pos, ent_j, per, C, kw, H, psum, p_cap, send, ff ? 1 : 0,
+                                gstage, auc.hist, auc.stripes, auc.metrics, auc.step_counter, ovf,
+                                ovf_host, groups);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
@@ -2922,24 +2923,21 @@ void tpf_pack_grads(int64_t n, int bits, int G, const int32_t* cnt, const int32_
 void tpf_step(int64_t n, int bits, const int32_t* cntA, const int32_t* posA, const uint16_t* jA,
               const uint32_t* slotA, const float* psum, int64_t p_cap, const int32_t* cntB,
               const uint64_t* uniqB, const int32_t* posB, const uint16_t* jB, uint32_t* slotB,
-              float* w_ent, int64_t w_cap, void* slots, int64_t cap, uint64_t home_base,
-              uint64_t home_m, int init_type, float init_v, float init_s, uint64_t seed,
-              int32_t* err, int32_t* inserted, int algo, int lr_type, float alpha, float beta,
-              float l1, float l2, float grad_scale, float max_delta, double* stats,
-              int acc_stripes, uint32_t* hist, int nbins, int hist_stripes, double* metrics,
-              int64_t* step_counter, hipStream_t st) {
+              float* w_ent, int64_t w_cap, const TableRef& t, const KeyInit& init, int32_t* err,
+              int32_t* inserted, const UpdateParams& p, const StripedAcc& stats,
+              const AucOut& auc, hipStream_t st) {
   if (n <= 0) return;
-  if (hist && nbins != 2048) throw std::runtime_error("tpf_step: the fused AUC needs 2048 bins");
-  if (cap > (int64_t)1 << 32) throw std::runtime_error("tpf_step: > 2^32 slots (u32 slot ids)");
+  if (auc.hist && auc.nbins != 2048)
+    throw std::runtime_error("tpf_step: the fused AUC needs 2048 bins");
+  if (t.cap > (int64_t)1 << 32) throw std::runtime_error("tpf_step: > 2^32 slots (u32 slot ids)");
   int lg = 0;
-  while ((1ll << lg) < cap) ++lg;
-  UpdateParams p{algo, lr_type, alpha, beta, l1, l2, grad_scale, max_delta};
+  while ((1ll << lg) < t.cap) ++lg;
   const int groups = tpf_groups(n, bits);
-  tpf_step_kernel<<<(unsigned)groups + (cntA && hist ? 1u : 0u), tpf::kThr, 0, st>>>(
+  tpf_step_kernel<<<(unsigned)groups + (cntA && auc.hist ? 1u : 0u), tpf::kThr, 0, st>>>(
       cntA != nullptr, cntA, posA, jA, slotA, psum, p_cap, cntB != nullptr, cntB, uniqB, posB,
-      jB, slotB, w_ent, w_cap, (Slot*)slots, (uint64_t)(cap - 1), home_base, home_m, 64 - lg,
-      init_type, init_v, init_s, seed, err, inserted, p, stats, acc_stripes,
-      cntA ? hist : nullptr, nbins, hist_stripes, metrics, step_counter, groups);
+      jB, slotB, w_ent, w_cap, (Slot*)t.slots, (uint64_t)(t.cap - 1), t.home_base, t.home_m,
+      64 - lg, init.type, init.v, init.s, init.seed, err, inserted, p, stats.ptr, stats.stripes,
+      cntA ? auc.hist : nullptr, auc.nbins, auc.stripes, auc.metrics, auc.step_counter, groups);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
@@ -3067,17 +3065,16 @@ void tp_fwd_bwd_csr(const uint16_t* rep, const int32_t* dcnt, const int32_t* ent
 void tp_seg_update(const int32_t* pos_s, const int32_t* segid, int64_t n, const int32_t* n_ent,
                    const float* psum, const int32_t* seg_start, const int32_t* n_uniq,
                    unsigned long long* acc, int64_t u_cap, const int64_t* slot_idx, void* slots,
-                   int64_t cap, int algo, int lr_type, float alpha, float beta, float l1, float l2,
-                   float grad_scale, float max_delta, double* stats, int acc_stripes,
-                   uint32_t* hist, int nbins, int hist_stripes, double* metrics,
-                   int64_t* step_counter, hipStream_t st) {
+                   int64_t cap, const UpdateParams& p, const StripedAcc& stats,
+                   const AucOut& auc, hipStream_t st) {
   if (n <= 0) return;
-  if (hist && nbins != 2048) throw std::runtime_error("tp_seg_update: the fused AUC needs 2048 bins");
+  if (auc.hist && auc.nbins != 2048)
+    throw std::runtime_error("tp_seg_update: the fused AUC needs 2048 bins");
   const TpGeom g = tp_geom(n, 31);
-  UpdateParams p{algo, lr_type, alpha, beta, l1, l2, grad_scale, max_delta};
   tp_seg_update_kernel<<<grid_for(g.N, 256, 2048), 256, 0, st>>>(
       pos_s, segid, g.N, n_ent, psum, g.N, seg_start, n_uniq, acc, u_cap, slot_idx,
-      (Slot*)slots, cap, p, stats, acc_stripes, hist, nbins, hist_stripes, metrics, step_counter);
+      (Slot*)slots, cap, p, stats.ptr, stats.stripes, auc.hist, auc.nbins, auc.stripes,
+      auc.metrics, auc.step_counter);
   PSAMD_HIP_CHECK(hipGetLastError());
 }
 
