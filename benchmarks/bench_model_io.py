@@ -14,6 +14,12 @@
 * Stages of the device paths, each timed on its own: selection + sort, the format kernels
   per chunk, a device-to-host copy of the text, a plain write of the text to a file; a
   plain read of the file, the parse kernels per chunk, the table insert.
+* Warm start (``--rows warm`` runs this row alone), from the same file into a fresh
+  ``SparseLRTrainer``: ``load_model`` (file -> parse -> kv_seed per chunk, one stream)
+  against the composed path -- ``read_text_models_device`` (the whole model in HBM) + ``mix``
+  + owner mask + the FTRL ``z`` in torch + ``KVTable.load`` -- in alternation, best of
+  ``--repeats``; the two tables are compared; peak HBM of each above what was allocated
+  before it (``torch.cuda.max_memory_allocated``); kv_seed's own time (events around it).
 
 Prints one JSON line; progress goes to stderr."""
 from __future__ import annotations
@@ -33,6 +39,81 @@ def log(*a):
     print("[bench_model_io]", *a, file=sys.stderr, flush=True)
 
 
+def warm_start_row(pat: str, N: int, a, res: dict):
+    """load_model against the composed path on fresh trainers; fills ``res``."""
+    import torch
+
+    from parameter_server_amd.models import SparseLRConfig, SparseLRTrainer
+    from parameter_server_amd.ops.keymix import mix
+    from parameter_server_amd.ops.modeltext import read_text_models_device
+
+    dev = torch.device("cuda")
+    cap = 1 << max(10, (4 * N - 1).bit_length() - 1)  # load in (0.25, 0.5]
+    cfg = SparseLRConfig(num_features=0, minibatch=1024, table_capacity=cap)
+
+    def fused(tr):
+        evs = []
+        seed = tr.table.seed
+
+        def timed(*args, **kw):
+            e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+            e0.record()
+            seed(*args, **kw)
+            e1.record()
+            evs.append((e0, e1))
+        tr.table.seed = timed
+        r = tr.load_model(pat, chunk_bytes=a.chunk_bytes)
+        torch.cuda.synchronize()
+        assert r["seeded"] == N and r["deferred_chunks"] == 0, r
+        return sum(e0.elapsed_time(e1) for e0, e1 in evs) / 1e3
+
+    def composed(tr):
+        rk, ww, entries, deferred = read_text_models_device(pat, dev, chunk_bytes=a.chunk_bytes)
+        h = mix(rk, tr.bits)
+        own = tr.part.owner_of(h) == tr.rank
+        c = tr.cfg
+        z = -(ww * ((0.0 + c.beta) / c.alpha + c.l2) + torch.copysign(torch.full_like(ww, c.l1), ww))
+        tr.table.load(h[own], ww[own], z[own], torch.zeros_like(ww)[own])
+        assert entries == N and deferred == 0
+        return 0.0
+
+    times = {"load_model": [], "composed": []}
+    peaks, kernel, tabs = {}, [], {}
+    fused(SparseLRTrainer(cfg, device=dev))  # (warm-up)
+    for r in range(a.repeats):
+        for name, fn in (("composed", composed), ("load_model", fused)):
+            tabs.pop(name, None)
+            tr = SparseLRTrainer(cfg, device=dev)
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            t0 = time.perf_counter()
+            ks = fn(tr)
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+            times[name].append(t)
+            peaks[name] = torch.cuda.max_memory_allocated() - base
+            if name == "load_model":
+                kernel.append(ks)
+            tabs[name] = tr
+            log(f"warm start {name} #{r}: {t:.3f} s, {N / t / 1e6:.2f} M entries/s, "
+                f"peak HBM above the trainer {peaks[name] / 2 ** 20:.0f} MiB")
+    (ak, aw, az, an), (bk, bw, bz, bn) = (tabs[m].table.occupied()
+                                          for m in ("load_model", "composed"))
+    ao, bo = torch.argsort(ak), torch.argsort(bk)
+    assert torch.equal(ak[ao], bk[bo]) and torch.equal(aw[ao].view(torch.int32),
+                                                       bw[bo].view(torch.int32))
+    torch.testing.assert_close(az[ao], bz[bo], rtol=1e-6, atol=0)
+    for name in times:
+        t = min(times[name])
+        res[f"warm_{name}_s"] = round(t, 4)
+        res[f"warm_{name}_entries_per_s"] = round(N / t)
+        res[f"warm_{name}_peak_hbm_bytes"] = int(peaks[name])
+    res["warm_kv_seed_kernels_s"] = round(min(kernel), 4)
+    res["warm_table_capacity"] = cap
+    res["warm_tables_identical"] = True
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entries", type=int, default=20_000_000)
@@ -40,6 +121,8 @@ def main():
     ap.add_argument("--chunk-entries", type=int, default=1 << 21)
     ap.add_argument("--chunk-bytes", type=int, default=32 << 20)
     ap.add_argument("--dir", default=None, help="where the model files go (default: a temp dir)")
+    ap.add_argument("--rows", choices=("all", "warm"), default="all",
+                    help="warm: only the warm-start row (the file is written by one device save)")
     a = ap.parse_args()
 
     import torch
@@ -87,6 +170,12 @@ def main():
     res = {"entries": N, "chunk_entries": a.chunk_entries, "chunk_bytes": a.chunk_bytes}
     paths = {m: os.path.join(out, m, "m_S0") for m in ("host", "device")}
     save("device", paths["device"])  # (warm-up: allocator, pinned memory, file cache)
+    if a.rows == "warm":
+        warm_start_row(os.path.join(out, "device", "m_S.*"), N, a, res)
+        if a.dir is None:
+            shutil.rmtree(out, ignore_errors=True)
+        print(json.dumps(res))
+        return
     times = {"host": [], "device": []}
     for r in range(a.repeats):
         for mode in ("host", "device"):
@@ -189,6 +278,8 @@ def main():
     sync()
     res["load_stage_table_insert_s"] = round(time.perf_counter() - t0, 4)
     assert occ == entries == N
+    del s, rk, ww
+    warm_start_row(pat, N, a, res)
     if a.dir is None:
         shutil.rmtree(out, ignore_errors=True)
     print(json.dumps(res))

@@ -14,7 +14,14 @@ torchrun rank is one GPU = a colocated worker + server shard:
 * ``async_sgd`` -> ``SparseLRTrainer`` (models/sparse_lr.py) through ``lm_to_sparse_lr``:
   minibatch, loss, FTRL / AdaGrad / SGD, learning rate, L1 / L2, tail filter,
   fixing-float, ``max_delay`` -> ``ssp:max_delay`` (0: the reference's unbounded
-  pipelining = ``asp`` with more than one rank). The rank's files (``divide_files``,
+  pipelining = ``asp`` with more than one rank). A ``model_input`` next to
+  ``training_data`` is a WARM START: before the first pass every rank streams the
+  ``key\\tweight`` files matching ``model_input.file[0]`` into its shard with the optimizer
+  state that reproduces each weight (``SparseLRTrainer.load_model``; the summary gains
+  ``warm_start_entries`` / ``warm_start_seeded`` / ``warm_start_deferred_chunks``; the
+  reference reads ``model_input`` only to evaluate). ``-num_features`` must be the value
+  the model was trained with (another one raises when a key does not fit, and otherwise
+  seeds other keys). The rank's files (``divide_files``,
   round-robin as postmaster.cc:6-15) stream through ``DeviceFeeder``: C++ parser
   threads -> pinned double-buffered host slots -> async host->HBM copies on a side
   stream, overlapped with the step. Rows of one width without values take the fused
@@ -138,6 +145,12 @@ def run_async_sgd(lm, comm, device, flags, printer=None) -> dict:
         over["consistency"] = "asp"  # the reference's unbounded pipelining (async_sgd.h:219-238)
     cfg = lm_to_sparse_lr(lm, **over)
     tr = SparseLRTrainer(cfg, comm, device)
+    warm = None
+    if lm.has("model_input"):  # warm start: continue from the stored model (collective)
+        warm = tr.load_model(lm.model_input.file[0])
+        if rank == 0 and not flags.quiet:
+            print(f"warm start: {warm['entries']} model entries, {warm['seeded']} seeded on "
+                  f"rank 0", file=sys.stderr)
     td = lm.training_data
     cache_dir, tmp_cache = _cache_dir(flags, sgd.num_data_pass, rank)
     feeder = DeviceFeeder(rank_files(td, G, rank), td.text, cfg.minibatch, tr.max_nnz, device,
@@ -227,6 +240,9 @@ def run_async_sgd(lm, comm, device, flags, printer=None) -> dict:
            "deferred_chunks": feeder.deferred_chunks,
            "agreed_steps": agreed, "host_feed_wait_s": t_feed, "host_step_issue_s": t_step,
            "table_capacity": p["table_capacity"], "table_grown": p["table_grown"]}
+    if warm is not None:
+        out.update(warm_start_entries=warm["entries"], warm_start_seeded=warm["seeded"],
+                   warm_start_deferred_chunks=warm["deferred_chunks"])
     if tmp_cache:
         import shutil
 

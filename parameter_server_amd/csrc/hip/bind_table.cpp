@@ -128,6 +128,30 @@ void psamd_bind::register_table(py::module_& m) {
     psamd::kv_census(slots.data_ptr(), cap, ptr<unsigned long long>(out), cur_stream());
     return out;
   });
+  // warm start: (raw key, weight) pairs seeded with the optimizer state that reproduces
+  // each weight; counts: the striped int64 [64 x 16] counters the launch adds to
+  m.def("kv_seed", [](Tensor slots, Tensor raw, Tensor w, int bits, uint64_t lo, uint64_t last,
+                      int algo, int lr_type, double alpha, double beta, double l1, double l2,
+                      double n0, Tensor counts, optional<Tensor> stats, optional<Tensor> err,
+                      uint64_t home_base, uint64_t home_m) {
+    const psamd::TableRef t = table_ref(slots, home_base, home_m);
+    chk(raw, at::kLong, "raw");
+    chk(w, at::kFloat, "w");
+    chk(counts, at::kLong, "counts");
+    check(w.numel() >= raw.numel(), "kv_seed: fewer weights than keys");
+    check(counts.numel() == psamd::kAccStripes * psamd::kAccStride,
+          "kv_seed: counts must be 64 x 16 int64");
+    check(alpha > 0 && n0 >= 0, "kv_seed: alpha > 0 and n0 >= 0");
+    check(last >= lo, "kv_seed: empty key range");
+    psamd::kv_seed(t, make_keymix(bits), ptr<uint64_t>(raw), ptr<float>(w), raw.numel(), lo,
+                   last, update_params(algo, lr_type, alpha, beta, l1, l2, 1.0, 0.0), (float)n0,
+                   ptr<unsigned long long>(counts), psamd::kAccStripes,
+                   striped_acc(stats, "stats"), optr<int32_t>(err, at::kInt, "err"),
+                   cur_stream());
+  }, py::arg("slots"), py::arg("raw"), py::arg("w"), py::arg("bits"), py::arg("lo"),
+     py::arg("last"), py::arg("algo"), py::arg("lr_type"), py::arg("alpha"), py::arg("beta"),
+     py::arg("l1"), py::arg("l2"), py::arg("n0"), py::arg("counts"), py::arg("stats"),
+     py::arg("err"), py::arg("home_base") = 0, py::arg("home_m") = 0);
   // growth: every occupied slot of `old_slots` into the larger, kv_init-ed `slots`;
   // returns the device count of slots moved (a 0-dim int64 tensor)
   m.def("kv_rehash", [](Tensor old_slots, Tensor slots, uint64_t home_base, uint64_t home_m,

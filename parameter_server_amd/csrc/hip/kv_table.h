@@ -17,6 +17,15 @@ void kv_init(void* slots, int64_t cap, hipStream_t st);
 // u64 count of slots moved; err (may be null): bit 0 = new table exhausted
 void kv_rehash(const void* old_slots, int64_t old_cap, const TableRef& t,
                unsigned long long* moved, int stripes, int32_t* err, hipStream_t st);
+// warm start: n (raw key, weight) pairs into the table with the optimizer state of rule p
+// that reproduces each weight (n0: prior gradient norm); keeps mixed keys in [lo, last];
+// counts: count_stripes x kAccStride u64 [seeded, overwritten, foreign, out_of_range,
+// skipped], added to; stats.ptr (may be null): [0] += change of the non-zero weight
+// count; err (may be null): bit 0 = table full. Runs alone on the table
+void kv_seed(const TableRef& t, KeyMix km, const uint64_t* raw, const float* w, int64_t n,
+             uint64_t lo, uint64_t last, const UpdateParams& p, float n0,
+             unsigned long long* counts, int count_stripes, const StripedAcc& stats,
+             int32_t* err, hipStream_t st);
 // slot index (-1: absent / full) and weight of n keys; out_w, err, inserted may be null
 void kv_resolve(const TableRef& t, const uint64_t* keys, int64_t n, const int32_t* n_dev,
                 int64_t* out_slot, float* out_w, bool insert, const KeyInit& init, int32_t* err,

@@ -664,8 +664,136 @@ __global__ __launch_bounds__(256) void kv_rehash_kernel(
   }
 }
 
+// Warm start: seed a parsed chunk of a key<TAB>weight model file into the live table with
+// the optimizer state that REPRODUCES each weight (a table loaded with w and z = n = 0
+// forgets the weight at the key's first FTRL update: z += g - sigma * w_old, w = prox(-z eta)).
+//   inv_eta0 = 1 / alpha (constant) or (n0 + beta) / alpha (decay); never 1 / eta, so that
+//              beta = n0 = 0 gives 0 and not a division by zero
+//   FTRL:    n = n0, z = -(w * (inv_eta0 + l2) + copysign(l1, w))   (the inverse of
+//            soft_threshold_prox(-z eta0, eta0, l1, l2); every term has the sign of w)
+//   AdaGrad: z = 0, n = n0^2.   SGD: z = n = 0 (cnt = 0).
+// Per entry: a raw key outside [0, 2^bits) is counted and dropped, the key is mixed, kept
+// when its mixed value lies in [lo, last] (this shard's range), dropped when w is 0 or NaN,
+// then looked up or inserted by resolve_key's rules (the table's own home map, CAS claim,
+// trip bound mask + 1, err bit 0 when the table is full) and the WHOLE slot is written as
+// two 16-byte stores: {key, w (the file's bits), z} and {n, acc = 0, cnt = 0, kSlotInit}.
+//
+// The probes are random 32-byte lines and latency bound (as predict.hip): a thread takes
+// kSeedBatch entries per round and issues all their first probes -- one 16-byte load of
+// {key, w, z} at a clamped, in-range address for entries past the end -- before it looks at
+// any. A stale first probe can only read kEmptyKey for a slot claimed meanwhile; the CAS
+// decides. The kernel runs alone on the table (the caller flushed; no step in flight).
+// counts: striped u64 (acc_stripe layout) [seeded, overwritten, foreign, out_of_range,
+// skipped]; stats[0] += the change of the table's non-zero weight count.
+constexpr int kSeedBatch = 4;
+enum SeedCount : int { kSeedNew = 0, kSeedOver, kSeedForeign, kSeedRange, kSeedSkip, kSeedCounts };
+
+__global__ __launch_bounds__(256) void kv_seed_kernel(
+    Slot* __restrict__ slots, uint64_t mask, uint64_t home_base, uint64_t home_m, int home_shr,
+    KeyMix km, const uint64_t* __restrict__ raw, const float* __restrict__ wv, int64_t n,
+    uint64_t lo, uint64_t last, UpdateParams p, float n0,
+    unsigned long long* __restrict__ counts, int count_stripes, double* __restrict__ stats,
+    int acc_stripes, int32_t* __restrict__ err) {
+  const float inv_eta0 = p.lr_type == kLrConstant ? 1.f / p.alpha : (n0 + p.beta) / p.alpha;
+  const float zscale = inv_eta0 + p.l2;
+  const float n_seed = p.algo == kFTRL ? n0 : (p.algo == kAdaGrad ? n0 * n0 : 0.f);
+  int c_new = 0, c_over = 0, c_foreign = 0, c_range = 0, c_skip = 0, dnnz = 0;
+  const int64_t threads = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i0 < n;
+       i0 += threads * kSeedBatch) {
+    uint64_t h[kSeedBatch], idx[kSeedBatch];
+    float w[kSeedBatch];
+    uint4 v[kSeedBatch];
+    bool act[kSeedBatch];
+#pragma unroll
+    for (int j = 0; j < kSeedBatch; ++j) {
+      const int64_t i = i0 + j * threads;
+      const bool ok = i < n;
+      const int64_t ic = ok ? i : n - 1;  // (n > 0 here: i0 < n)
+      const uint64_t r = raw[ic];
+      w[j] = wv[ic];
+      h[j] = mix_key(r, km);
+      const bool in_bits = r <= km.mask;
+      const bool owned = h[j] >= lo && h[j] <= last;
+      const bool keep = w[j] != 0.f && w[j] == w[j];
+      act[j] = ok && in_bits && owned && keep;
+      c_range += ok && !in_bits;
+      c_foreign += ok && in_bits && !owned;
+      c_skip += ok && in_bits && owned && !keep;
+    }
+#pragma unroll
+    for (int j = 0; j < kSeedBatch; ++j) {
+      idx[j] = home_slot(h[j], mask, home_base, home_m, home_shr) & mask;
+      v[j] = *reinterpret_cast<const uint4*>(slots + idx[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < kSeedBatch; ++j) {
+      if (!act[j]) continue;
+      uint64_t at = idx[j];
+      uint64_t k = ((uint64_t)v[j].y << 32) | v[j].x;
+      float w_old = __uint_as_float(v[j].z);
+      bool found = false, fresh = false;
+      for (uint64_t probe = 0; probe <= mask; ++probe) {  // TRIP BOUND: mask + 1 slots
+        if (probe) {
+          k = slots[at].key;
+          w_old = slots[at].w;
+        }
+        if (k == kEmptyKey) {
+          k = atomicCAS((unsigned long long*)&slots[at].key, (unsigned long long)kEmptyKey,
+                        (unsigned long long)h[j]);
+          if (k == kEmptyKey) {
+            found = fresh = true;
+            break;
+          }
+          w_old = 0.f;  // (claimed meanwhile: by this launch, counted as a repeat if k == h)
+        }
+        if (k == h[j]) {
+          found = true;
+          break;
+        }
+        at = (at + 1) & mask;
+      }
+      if (!found) {
+        if (err) atomicOr(err, 1);  // table full
+        continue;
+      }
+      const float z = p.algo == kFTRL ? -(w[j] * zscale + copysignf(p.l1, w[j])) : 0.f;
+      uint4* d = reinterpret_cast<uint4*>(slots + at);
+      d[0] = make_uint4((uint32_t)h[j], (uint32_t)(h[j] >> 32), __float_as_uint(w[j]),
+                        __float_as_uint(z));
+      d[1] = make_uint4(__float_as_uint(n_seed), 0u, 0u, kSlotInit);
+      c_new += fresh;
+      c_over += !fresh;
+      dnnz += fresh || w_old == 0.f;
+    }
+  }
+  const int tot[kSeedCounts] = {wave_sum(c_new), wave_sum(c_over), wave_sum(c_foreign),
+                                wave_sum(c_range), wave_sum(c_skip)};
+  dnnz = wave_sum(dnnz);
+  if ((threadIdx.x & 63) == 0) {
+    unsigned long long* cs = counts + (int64_t)(blockIdx.x % count_stripes) * kAccStride;
+#pragma unroll
+    for (int c = 0; c < kSeedCounts; ++c)
+      if (tot[c]) atomicAdd(&cs[c], (unsigned long long)tot[c]);
+    if (stats && dnnz) atomicAdd(&acc_stripe(stats, acc_stripes)[0], (double)dnnz);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Host launchers
+void kv_seed(const TableRef& t, KeyMix km, const uint64_t* raw, const float* w, int64_t n,
+             uint64_t lo, uint64_t last, const UpdateParams& p, float n0,
+             unsigned long long* counts, int count_stripes, const StripedAcc& stats,
+             int32_t* err, hipStream_t st) {
+  if (n <= 0) return;
+  int lg = 0;
+  while ((1ll << lg) < t.cap) ++lg;
+  kv_seed_kernel<<<grid_for((n + kSeedBatch - 1) / kSeedBatch, 256), 256, 0, st>>>(
+      (Slot*)t.slots, (uint64_t)(t.cap - 1), t.home_base, t.home_m, 64 - lg, km, raw, w, n, lo,
+      last, p, n0, counts, count_stripes, stats.ptr, stats.stripes, err);
+  PSAMD_HIP_CHECK(hipGetLastError());
+}
+
 void kv_rehash(const void* old_slots, int64_t old_cap, const TableRef& t,
                unsigned long long* moved, int stripes, int32_t* err, hipStream_t st) {
   int lg = 0;

@@ -933,6 +933,112 @@ class SparseLRTrainer(PaddedExchange, ExactExchange, P2PExchange, TableGrowth):
                         sd["n"].to(self.device)[own])
         self.step_count = int(sd.get("step", 0))
 
+    def load_model(self, pattern: str, text_io: str = "auto", n0: float = 0.0,
+                   chunk_bytes: int = 32 << 20) -> dict:
+        """Warm start: continue training from stored ``key\\tweight`` model files (what
+        ``save_model``, the reference and Darlin write: weights only). ``pattern``,
+        ``text_io`` and the fallback rules are ``ModelScorer.from_text``'s: a regex or glob
+        of ``<prefix>_<NodeID>`` files; "auto" parses the text on the GPU when the table is
+        on one, "host" is the dict reader, "device" on a CPU table raises. Collective when
+        G > 1: every rank reads every file and keeps the keys it owns, so a model saved by
+        any number of ranks loads into any world size.
+
+        Every kept weight is seeded with the optimizer state that reproduces it
+        (``KVTable.seed``): FTRL gets the ``z`` whose proximal step gives back ``w``, so the
+        first update continues from the stored weight instead of forgetting it. ``n0 >= 0``
+        is the prior gradient norm of every key (0: fresh per-key learning rates).
+
+        Streaming: each chunk of at most ``chunk_bytes`` goes file -> pinned -> HBM ->
+        ``modeltext_parse`` -> ``kv_seed`` on one stream, the next chunk's file read under
+        the current chunk's kernels; the model is never held whole. A chunk the device parser
+        declines is parsed by the host rules and seeded all the same (``deferred_chunks``).
+        A key that repeats (the kernel's ``overwritten`` count) or a line longer than a
+        chunk restarts the load through the dict reader, where the later line wins
+        (``deferred_chunks`` >= 1). With ``table_growth`` the table makes room before each
+        chunk; without it a table that fills raises 'KVTable full'.
+
+        Defined on a fresh trainer only (no step taken, empty table): ``ValueError``
+        otherwise, and when a key lies outside [0, 2^bits) (the model was stored with another
+        ``num_features``). The tail filter's CountMin sketch is not part of a text model
+        and starts empty: with ``tail_feature_freq`` on, a seeded key is filtered from the
+        minibatches until the sketch has seen it more than that many times; its stored
+        weight is kept meanwhile. Returns (and leaves in ``last_load``) {"entries",
+        "seeded", "foreign", "deferred_chunks", "table_capacity"}: ``entries`` the pairs
+        read, ``seeded`` / ``foreign`` those this rank kept / left to the other ranks."""
+        from ..ops.modeltext import (MAX_CHUNK_BYTES, _LineTooLong, iter_text_model_chunks,
+                                     read_pairs_host)
+
+        if text_io not in ("auto", "host", "device"):
+            raise ValueError(f"load_model: text_io must be auto, host or device, not {text_io!r}")
+        if text_io == "device" and not self.table.gpu:
+            raise ValueError("load_model: text_io='device' needs the table on a GPU")
+        chunk_bytes = int(chunk_bytes)
+        if not 64 <= chunk_bytes <= MAX_CHUNK_BYTES:
+            raise ValueError("load_model: chunk_bytes must be in [64, 2^30]")
+        if n0 < 0:
+            raise ValueError("load_model: n0 must be >= 0")
+        if self.step_count != 0 or self.table.census()[0] != 0:
+            raise ValueError("load_model needs a fresh trainer: no step taken and an empty table")
+        self.flush()
+        self._table_changed()  # the table changes under any pull issued ahead
+        tb, g = self.table, self._growth
+        lo, hi = tb.key_range or self.part.range_of(self.rank)
+        counts = tb.new_seed_counts()
+        entries = deferred = 0
+
+        def seed(raw, w):
+            nonlocal entries
+            entries += raw.numel()
+            self._growth_room(raw.numel(), exact=False)  # (collective when G > 1)
+            tb.seed(raw, w, self.bits, lo, hi, self.rule, n0, stats=self.stats, counts=counts)
+
+        def seed_host():
+            """The whole model by the dict reader (the later line of a repeated key wins:
+            reported as at least one deferred chunk)."""
+            nonlocal deferred
+            raw, w, repeated = read_pairs_host(pattern)
+            deferred = max(int(repeated), deferred)
+            seed(raw, w)
+
+        def restart():
+            """Everything seeded so far dropped; the whole model by the dict reader."""
+            nonlocal entries, deferred
+            tb.clear()
+            counts.zero_()
+            self.stats.view(-1, 16)[:, 0].zero_()  # the cumulative nnz column
+            if g is not None:
+                g.bound = 0
+            entries, deferred = 0, max(1, deferred)
+            seed_host()
+
+        if text_io != "host" and tb.gpu:
+            try:
+                for raw, w, was_deferred in iter_text_model_chunks(pattern, self.device,
+                                                                   chunk_bytes):
+                    deferred += was_deferred
+                    seed(raw, w)
+            except _LineTooLong:
+                restart()
+        else:
+            seed_host()
+        c = tb.seed_counts(counts)
+        repeats = c["overwritten"]
+        if self.G > 1 and not self._loopback:  # (a repeat on any rank: all restart together)
+            repeats = int(self.comm.all_reduce_(self._to_comm(
+                torch.tensor([float(repeats)], dtype=torch.float64)), op="max").item())
+        if repeats and not c["out_of_range"]:
+            restart()
+            c = tb.seed_counts(counts)
+        if c["out_of_range"]:
+            raise ValueError(
+                f"load_model: {c['out_of_range']} keys of {pattern!r} lie outside [0, 2^{self.bits}): "
+                f"the model was stored with another num_features")
+        if tb.gpu:
+            self.check_ok()  # (a table that filled: 'KVTable full', on every rank together)
+        self.last_load = {"entries": entries, "seeded": c["seeded"], "foreign": c["foreign"],
+                          "deferred_chunks": deferred, "table_capacity": tb.capacity}
+        return dict(self.last_load)
+
     # ------------------------------------------------------------ scoring
     def scorer(self):
         """A ``ModelScorer`` (models/scorer.py) over the current weights, after ``flush()``.

@@ -213,14 +213,26 @@ class TableGrowth:
     def _growth_load(self, own: torch.Tensor):
         """``load_state_dict`` with growth on: make room for the keys this rank owns (the
         true entries of ``own``) first."""
+        if self._growth is not None:
+            self._growth_room(int(own.sum()))
+
+    def _growth_room(self, incoming: int, exact: bool = True):
+        """Make room for ``incoming`` keys about to be loaded into the table (collective
+        when G > 1: every rank calls it with the same sequence of ``exact`` / bounds).
+        ``exact=False`` (``load_model``, once per chunk with the chunk's entry count --
+        the same on every rank): the occupancy is counted only when the host's upper
+        bound says the load could pass ``table_grow_at``."""
         g = self._growth
         if g is None or g.refused:
             return
+        cap = self.table.capacity
+        if not exact and g.bound + incoming <= g.at * cap:
+            g.bound += incoming
+            return
         self._growth_prepare()
-        need = int(self.table.census()[0]) + int(own.sum())
+        need = int(self.table.census()[0]) + int(incoming)
         if g.reduce_max is not None:  # (the fullest shard decides: equal capacities)
             need = g.reduce_max(need)
-        cap = self.table.capacity
         if need > g.at * cap:
             while need > g.at / 2 * cap:
                 cap *= 2

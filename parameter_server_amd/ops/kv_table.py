@@ -193,6 +193,111 @@ class KVTable:
         self.check_ok()
         return slot
 
+    # ------------------------------------------------------------- warm start
+    SEED_COUNTS = ("seeded", "overwritten", "foreign", "out_of_range", "skipped")
+
+    def clear(self):
+        """Every slot empty again (capacity, init rule and home mapping stay)."""
+        if self.gpu:
+            hipops().kv_init(self.slots)
+        else:
+            core().kv_init(ptr(self.slots), self.capacity)
+        self.num_inserted = 0
+
+    def new_seed_counts(self) -> torch.Tensor:
+        """The striped counters ``seed(..., counts=)`` adds to over several calls."""
+        return torch.zeros(64 * 16, dtype=torch.int64, device=self.device)
+
+    def seed_counts(self, counts: torch.Tensor) -> dict:
+        """``counts`` as {"seeded", "overwritten", "foreign", "out_of_range", "skipped"}
+        (GPU: the one host sync of a seeded load)."""
+        tot = counts.view(-1, 16).sum(0)[:len(self.SEED_COUNTS)].tolist()
+        return dict(zip(self.SEED_COUNTS, (int(v) for v in tot)))
+
+    def seed(self, raw_keys: torch.Tensor, w: torch.Tensor, bits: int, lo: int, hi: int,
+             rule: UpdateRule, n0: float = 0.0, stats: torch.Tensor | None = None,
+             counts: torch.Tensor | None = None):
+        """Warm start: (raw key, weight) pairs of a stored model into this table, with the
+        optimizer state of ``rule`` that REPRODUCES each weight (kv_table.hip kv_seed; a
+        table loaded with w and z = n = 0 forgets w at a key's first FTRL update).
+
+        ``raw_keys``: int64 bit patterns; a key outside [0, 2^bits) (bits < 64) is counted
+        as ``out_of_range``. Kept: keys whose mixed value lies in [lo, hi) (others:
+        ``foreign``) with a weight that is neither 0 nor NaN (others: ``skipped``). Each is
+        looked up or inserted (``seeded`` / ``overwritten``) and its whole slot written: w
+        the given bits, acc = cnt = 0, the published-init flag, and with ``n0 >= 0`` a prior
+        gradient norm, inv_eta0 = 1 / alpha (constant) or (n0 + beta) / alpha (decay):
+        FTRL n = n0, z = -(w (inv_eta0 + l2) + copysign(l1, w)); AdaGrad z = 0, n = n0^2;
+        SGD z = n = 0. ``stats[0]`` gains the change of the non-zero weight count.
+
+        Returns the counts as a dict; with ``counts`` (``new_seed_counts``) they are added
+        there instead and nothing is read back (``seed_counts`` at the end). Nothing else
+        may be using the table. A repeated key within or across calls is ``overwritten``
+        with no promise which weight stays."""
+        algo, lr_type, alpha, beta, l1, l2 = rule.args()[:6]
+        n0 = float(n0)
+        if n0 < 0 or alpha <= 0:
+            raise ValueError("KVTable.seed: n0 >= 0 and alpha > 0")
+        lo, hi = int(lo), int(hi)
+        if hi <= lo:
+            raise ValueError(f"KVTable.seed: empty key range [{lo}, {hi})")
+        raw_keys = raw_keys.to(self.device).contiguous()
+        w = w.to(self.device, torch.float32).contiguous()
+        if raw_keys.dtype != torch.int64 or raw_keys.shape != w.shape or raw_keys.dim() != 1:
+            raise ValueError("KVTable.seed: int64 key bit patterns and weights of one 1-d shape")
+        own = counts if counts is not None else self.new_seed_counts()
+        if self.gpu:
+            if raw_keys.numel():
+                hipops().kv_seed(self.slots, raw_keys, w, bits, lo, hi - 1, algo, lr_type, alpha,
+                                 beta, l1, l2, n0, own, stats, self._err, self.home_base,
+                                 self.home_m)
+        elif raw_keys.numel():
+            self._seed_host(raw_keys, w, bits, lo, hi, (algo, lr_type, alpha, beta, l1, l2), n0,
+                            stats, own)
+        return self.seed_counts(own) if counts is None else None
+
+    def _seed_host(self, raw, w, bits, lo, hi, rule, n0, stats, counts):
+        """The PyTorch reference of kv_seed: mix, range mask, resolve(insert), whole-slot
+        write with z in float32 in the kernel's operation order."""
+        from .keymix import mix, to_unsigned_order
+
+        algo, lr_type, alpha, beta, l1, l2 = rule
+        in_bits = torch.ones_like(raw, dtype=torch.bool) if bits == 64 else \
+            (raw >= 0) & (raw < (1 << bits))
+        h = mix(raw, bits)
+        hu = to_unsigned_order(h)  # (signed order == unsigned order)
+        owned = (hu >= lo - (1 << 63)) & (hu <= hi - 1 - (1 << 63))
+        keep = (w != 0) & ~torch.isnan(w)
+        act = in_bits & owned & keep
+        hk, wk = h[act].contiguous(), w[act]
+        pre, w_pre = self.resolve(hk, insert=False)
+        before = self.num_inserted
+        slot, _ = self.resolve(hk, insert=True, with_w=False)  # (a full table raises here)
+        fresh = self.num_inserted - before
+        # non-zero weights gained: every inserted key, and present ones that held 0
+        dnnz = fresh + int(((pre >= 0) & (w_pre == 0)).sum())
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32)  # noqa: E731
+        inv_eta0 = 1.0 / f32(alpha) if lr_type == LR_TYPES["constant"] else \
+            (f32(n0) + f32(beta)) / f32(alpha)
+        if algo == ALGOS["ftrl"]:
+            z = -(wk * (inv_eta0 + f32(l2)) + torch.copysign(f32(l1), wk))
+            n = f32(n0)
+        else:
+            z = torch.zeros_like(wk)
+            n = f32(n0) * f32(n0) if algo == ALGOS["adagrad"] else f32(0.0)
+        fl = self.slots.view(torch.float32)   # [cap, 8]: key | w z | n acc | cnt flags
+        it = self.slots.view(torch.int32)
+        fl[slot, 2], fl[slot, 3], fl[slot, 4], fl[slot, 5] = wk, z, n.expand_as(wk), 0.0
+        it[slot, 6], it[slot, 7] = 0, 2  # cnt, flags = kSlotInit (kv_slot.cuh)
+        c = counts.view(-1, 16)[0]
+        c[0] += fresh
+        c[1] += int(act.sum()) - fresh
+        c[2] += int((in_bits & ~owned).sum())
+        c[3] += int((~in_bits).sum())
+        c[4] += int((in_bits & owned & ~keep).sum())
+        if stats is not None:
+            stats.view(-1)[0] += float(dnnz)
+
     # ---------------------------------------------------------------- growth
     def grow(self, capacity: int) -> int:
         """Rehash every occupied slot, as the whole 32-byte record, into a table of

@@ -136,6 +136,26 @@ def pairs_of(model: dict[int, float]) -> tuple[torch.Tensor, torch.Tensor]:
     return raw, w
 
 
+class _CountingDict(dict):
+    """A model dict that counts its assignments (= the files' pairs)."""
+
+    sets = 0
+
+    def __setitem__(self, k, v):
+        self.sets += 1
+        super().__setitem__(k, v)
+
+
+def read_pairs_host(pattern: str) -> tuple[torch.Tensor, torch.Tensor, bool]:
+    """``pairs_of(read_text_models(pattern))`` and whether some key repeated (the later
+    line won)."""
+    model = _CountingDict()
+    for fn in find_model_files(pattern):
+        with open(fn) as f:
+            parse_model_lines(f, model)
+    return (*pairs_of(model), model.sets != len(model))
+
+
 def _host_chunk(raw: bytes) -> tuple[torch.Tensor, torch.Tensor]:
     """A chunk of whole lines by the host rules (text mode: decoding, newline translation)."""
     model: dict[int, float] = {}
@@ -158,6 +178,84 @@ def _last_newline(arr: np.ndarray, n: int) -> int:
     return 0
 
 
+def iter_text_model_chunks(pattern: str, device, chunk_bytes: int = 32 << 20,
+                           parse_ms: list | None = None):
+    """The file loop of the device reader, one chunk at a time: yields (raw keys int64 bit
+    patterns, float32 weights, deferred) per chunk of whole lines, in file order, on the GPU
+    ``device``. Each file is streamed through two pinned buffers in chunks of at most
+    ``chunk_bytes`` cut at a newline: file -> pinned -> HBM -> ``modeltext_parse`` on the
+    current stream, and the next chunk is read from the file while the device works on the
+    current one (and on whatever the consumer queued behind it).
+
+    The tensors of a chunk the parser took are VIEWS of the reader's one pair of device
+    buffers, valid until the generator is advanced: the consumer queues its work on them on
+    the current stream (or clones them) first. ``deferred``: the chunk set ``H_BAD``,
+    ``H_DEFER`` or ``H_CAP`` and was parsed by ``_host_chunk`` (fresh tensors). Raises
+    ``_LineTooLong`` for a line longer than a chunk. ``parse_ms``: gains each chunk's parse
+    kernel time."""
+    dev = torch.device(device)
+    files = find_model_files(pattern)
+    ops = hipops()
+    cap = chunk_bytes // 4 + 1  # (a line is at least "k\tw\n")
+    pins = [torch.empty(chunk_bytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
+    arrs = [p.numpy() for p in pins]
+    text_dev = torch.empty(chunk_bytes, dtype=torch.uint8, device=dev)
+    keys_buf = torch.empty(cap, dtype=torch.int64, device=dev)
+    w_buf = torch.empty(cap, dtype=torch.float32, device=dev)
+    hdr = torch.zeros(8, dtype=torch.int32, device=dev)
+    work = torch.empty(int(ops.textparse_work_words(chunk_bytes)), dtype=torch.int32, device=dev)
+    cur = torch.cuda.current_stream(dev)
+
+    def launch(i, n):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        text_dev[:n].copy_(pins[i][:n], non_blocking=True)
+        t0.record(cur)
+        ops.modeltext_parse(text_dev, n, keys_buf, w_buf, hdr, work)
+        t1.record(cur)
+        return i, n, t0, t1
+
+    def resolve(item):
+        i, n, t0, t1 = item
+        h = hdr.cpu().tolist()  # (the one read-back of the chunk)
+        if parse_ms is not None:
+            parse_ms.append(t0.elapsed_time(t1))
+        if h[H_CAP] or h[H_BAD] or h[H_DEFER] or h[H_ROWS] != h[H_NNZ]:
+            if h[H_CAP]:
+                hdr.zero_()  # (the capacity flag is sticky on the device)
+            k, v = _host_chunk(arrs[i][:n].tobytes())
+            return k.to(dev), v.to(dev), True
+        return keys_buf[:h[H_ROWS]], w_buf[:h[H_ROWS]], False
+
+    pending = None
+    slot = 0
+    for fn in files:
+        with open(fn, "rb") as f:
+            carry = np.empty(0, dtype=np.uint8)
+            while True:
+                arr = arrs[slot]
+                arr[:carry.size] = carry
+                got = f.readinto(memoryview(arr)[carry.size:])
+                n = carry.size + got
+                if got:
+                    cut = _last_newline(arr, n)
+                    if cut == 0 and n == chunk_bytes:
+                        raise _LineTooLong
+                else:
+                    cut = n  # (the end of the file: a last line without its newline)
+                carry = arr[cut:n].copy()
+                if pending is not None:
+                    item, pending = pending, None
+                    yield resolve(item)  # (the file read above ran under its kernels)
+                if cut:
+                    pending = launch(slot, cut)
+                    slot ^= 1
+                if not got:
+                    break
+    if pending is not None:
+        yield resolve(pending)
+
+
 def read_text_models_device(pattern: str, device, chunk_bytes: int = 32 << 20,
                             stats: dict | None = None):
     """Every ``key\\tweight`` file matching ``pattern`` (the files and the order of
@@ -177,74 +275,18 @@ def read_text_models_device(pattern: str, device, chunk_bytes: int = 32 << 20,
         return raw, w, raw.numel(), 0
     if not 64 <= chunk_bytes <= MAX_CHUNK_BYTES:
         raise ValueError("read_text_models_device: chunk_bytes must be in [64, 2^30]")
-    files = find_model_files(pattern)
-    ops = hipops()
-    cap = chunk_bytes // 4 + 1  # (a line is at least "k\tw\n")
-    pins = [torch.empty(chunk_bytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
-    arrs = [p.numpy() for p in pins]
-    text_dev = torch.empty(chunk_bytes, dtype=torch.uint8, device=dev)
-    keys_buf = torch.empty(cap, dtype=torch.int64, device=dev)
-    w_buf = torch.empty(cap, dtype=torch.float32, device=dev)
-    hdr = torch.zeros(8, dtype=torch.int32, device=dev)
-    work = torch.empty(int(ops.textparse_work_words(chunk_bytes)), dtype=torch.int32, device=dev)
-    cur = torch.cuda.current_stream(dev)
     parts_k, parts_w = [], []
     deferred = 0
     parse_ms = []
-
-    def launch(i, n):
-        t0 = torch.cuda.Event(enable_timing=True)
-        t1 = torch.cuda.Event(enable_timing=True)
-        text_dev[:n].copy_(pins[i][:n], non_blocking=True)
-        t0.record(cur)
-        ops.modeltext_parse(text_dev, n, keys_buf, w_buf, hdr, work)
-        t1.record(cur)
-        return i, n, t0, t1
-
-    def resolve(item):
-        nonlocal deferred
-        i, n, t0, t1 = item
-        h = hdr.cpu().tolist()  # (the one read-back of the chunk)
-        parse_ms.append(t0.elapsed_time(t1))
-        if h[H_CAP] or h[H_BAD] or h[H_DEFER] or h[H_ROWS] != h[H_NNZ]:
-            if h[H_CAP]:
-                hdr.zero_()  # (the capacity flag is sticky on the device)
-            deferred += 1
-            k, v = _host_chunk(arrs[i][:n].tobytes())
-            parts_k.append(k.to(dev))
-            parts_w.append(v.to(dev))
-        elif h[H_ROWS]:
-            parts_k.append(keys_buf[:h[H_ROWS]].clone())
-            parts_w.append(w_buf[:h[H_ROWS]].clone())
-
     try:
-        pending = None
-        slot = 0
-        for fn in files:
-            with open(fn, "rb") as f:
-                carry = np.empty(0, dtype=np.uint8)
-                while True:
-                    arr = arrs[slot]
-                    arr[:carry.size] = carry
-                    got = f.readinto(memoryview(arr)[carry.size:])
-                    n = carry.size + got
-                    if got:
-                        cut = _last_newline(arr, n)
-                        if cut == 0 and n == chunk_bytes:
-                            raise _LineTooLong
-                    else:
-                        cut = n  # (the end of the file: a last line without its newline)
-                    carry = arr[cut:n].copy()
-                    if pending is not None:
-                        resolve(pending)  # (the file read above ran under its kernels)
-                        pending = None
-                    if cut:
-                        pending = launch(slot, cut)
-                        slot ^= 1
-                    if not got:
-                        break
-        if pending is not None:
-            resolve(pending)
+        for k, v, was_deferred in iter_text_model_chunks(pattern, dev, chunk_bytes, parse_ms):
+            deferred += was_deferred
+            if was_deferred:
+                parts_k.append(k)
+                parts_w.append(v)
+            elif k.numel():  # (views of the reader's buffers: kept as copies)
+                parts_k.append(k.clone())
+                parts_w.append(v.clone())
     except _LineTooLong:  # (a line longer than a chunk: the host reader takes the model)
         raw, w = pairs_of(read_text_models(pattern))
         return raw.to(dev), w.to(dev), raw.numel(), 1
