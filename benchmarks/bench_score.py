@@ -19,6 +19,14 @@ minibatches, alternating in one process.
 * ``--app-rows``: the evaluation route of app/gpu.py on Criteo-shaped LIBSVM files
   (bench_app.py's generator), next to the CPU evaluator ``evaluate_model`` on the same
   files and model.
+* ``--predict-output DIR``: the cost of writing per-example predictions
+  (ops/scoretext.py). Criteo-shaped files are parsed once into a binary cache; then the
+  cached evaluation pass (``ModelScorer.evaluate`` over ``DeviceFeeder``, repeated until
+  ``--predict-rows`` rows went by) runs with no output, with the host writer and with the
+  device writer, alternated ``--repeats`` times in this process, the prediction file in
+  DIR. Reports examples/s of each, the device writer's per-chunk kernel and copy times
+  (device events around the launches) and its largest stage. Runs alone (the kernel paths
+  above are skipped).
 
 Prints one JSON line; timings are device events around ``--iters`` minibatches after
 ``--warmup``, repeated ``--repeats`` times per path in alternation."""
@@ -278,6 +286,105 @@ loss {{ type: LOGIT }}
     return out
 
 
+def bench_predict(a, dev):
+    """The cached evaluation pass with and without a prediction writer."""
+    import numpy as np
+    import torch
+    from bench_app import write_files
+
+    from parameter_server_amd.data.feeder import DeviceFeeder
+    from parameter_server_amd.models import ModelScorer
+    from parameter_server_amd.ops.keymix import key_bits_for
+    from parameter_server_amd.ops.scoretext import PredictionWriter
+    from parameter_server_amd.utils.checkpoint import write_text_model
+
+    N, B = 10 ** 8, a.minibatch
+    d = a.predict_output
+    os.makedirs(os.path.join(d, "model"), exist_ok=True)
+    per_pass = a.predict_file_rows // a.app_files * a.app_files
+    passes = max(1, -(-a.predict_rows // per_pass))
+    write_files(d, "criteo", per_pass, a.app_files, N=N)
+    files = sorted(os.path.join(d, f) for f in os.listdir(d) if f.startswith("part-"))
+    rng = np.random.default_rng(3)
+    mk = np.unique((N * rng.random(a.app_model_keys) ** 4).astype(np.uint64))
+    write_text_model(os.path.join(d, "model", "m_S0"), mk,
+                     rng.normal(0, 0.3, mk.size).astype(np.float32))
+    pattern, bits = os.path.join(d, "model", "m_S.*"), key_bits_for(N)
+    cache = os.path.join(d, "cache")
+
+    def feeder(parser="cpu"):
+        return DeviceFeeder(files, "LIBSVM", B, B * 39, dev, num_features=N, passes=1,
+                            shuffle=False, nthreads=16, ignore_slot=True, cache_dir=cache,
+                            io_threads=a.io_threads, parser=parser)
+
+    f = feeder("auto")
+    for b in f.iter_pass(0):  # (the text pass: writes the cache)
+        f.release(b)
+    torch.cuda.synchronize()
+    log(f"cache built: {f.num_examples} rows a pass, {passes} passes a run "
+        f"({passes * f.num_examples} rows), parser {f.parser}")
+
+    def run(mode):
+        sc = ModelScorer.from_text(pattern, bits, dev)
+        stats = {}
+        path = os.path.join(d, f"pred_{mode}")
+        w = None if mode == "none" else PredictionWriter(
+            path, dev, columns=tuple(a.predict_columns.split(",")), text_io=mode, stats=stats,
+            chunk_rows=a.predict_chunk_rows)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        rows = cached = 0
+        for _ in range(passes):
+            f = feeder()
+            sc.evaluate(f, predictions=w) if w is not None else sc.evaluate(f)
+            rows += f.num_examples
+            cached += f.cached_passes
+        if w is not None:
+            w.close()
+        torch.cuda.synchronize()
+        s = time.time() - t0
+        assert cached == passes, "the pass did not stream the cache"
+        assert w is None or stats["rows"] == rows
+        r = {"mode": mode, "rows": rows, "seconds": round(s, 4),
+             "examples_per_s": round(rows / s), "auc": sc.result()["auc"]}
+        if w is not None:
+            r.update(bytes=stats["bytes"], chunks=stats["chunks"],
+                     deferred_chunks=stats["deferred_chunks"],
+                     file_write_s=round(stats["file_write_s"], 4),
+                     host_format_s=round(stats["host_format_s"], 4))
+        if mode == "device":
+            fm, dm = sorted(stats["format_ms"]), sorted(stats["d2h_ms"])
+            stages = {"kernels": sum(fm) / 1e3, "d2h": sum(dm) / 1e3,
+                      "file_write": stats["file_write_s"]}
+            r.update(format_ms_per_chunk_median=round(fm[len(fm) // 2], 4),
+                     format_ms_per_chunk_max=round(fm[-1], 4),
+                     format_rows_per_s=round(rows / max(sum(fm) / 1e3, 1e-9)),
+                     d2h_ms_per_chunk_median=round(dm[len(dm) // 2], 4) if dm else None,
+                     header_wait_s=round(stats["header_wait_s"], 4),
+                     d2h_wait_s=round(stats["d2h_wait_s"], 4),
+                     stage_seconds={k: round(v, 4) for k, v in stages.items()},
+                     largest_stage=max(stages, key=stages.get))
+        log(json.dumps(r))
+        return r
+
+    run("none")  # (warm-up: page cache, allocator, pinned slots)
+    runs = [run(m) for _ in range(max(2, a.repeats)) for m in ("none", "host", "device")]
+    with open(os.path.join(d, "pred_host"), "rb") as fh, \
+            open(os.path.join(d, "pred_device"), "rb") as fd:
+        same = all(x == y for x, y in iter(lambda: (fh.read(1 << 24), fd.read(1 << 24)),
+                                           (b"", b"")))
+    assert same, "host and device prediction files differ"
+    best = {m: max(r["examples_per_s"] for r in runs if r["mode"] == m)
+            for m in ("none", "host", "device")}
+    out = {"B": B, "rows_per_run": runs[0]["rows"], "passes_per_run": passes,
+           "columns": a.predict_columns, "chunk_rows": a.predict_chunk_rows, "runs": runs,
+           "best_examples_per_s": best, "files_identical": same,
+           "device_over_host": round(best["device"] / best["host"], 3),
+           "device_over_none": round(best["device"] / best["none"], 3)}
+    log(f"best examples/s {best}; device / host {out['device_over_host']}")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minibatch", type=int, default=65536)
@@ -294,6 +401,16 @@ def main():
     ap.add_argument("--app-files", type=int, default=8)
     ap.add_argument("--app-model-keys", type=int, default=2_000_000)
     ap.add_argument("--app-parser", default="cpu,gpu")
+    ap.add_argument("--predict-output", default="",
+                    help="directory for the prediction-writer benchmark (runs alone)")
+    ap.add_argument("--predict-rows", type=int, default=120_000_000,
+                    help="rows per timed run (the cached pass feeds ~10^8 rows a second: fewer "
+                         "rows time the feeder's start-up)")
+    ap.add_argument("--predict-file-rows", type=int, default=4_000_000,
+                    help="rows of Criteo-shaped text generated and cached (one pass)")
+    ap.add_argument("--predict-columns", default="score", choices=("score", "label,score"))
+    ap.add_argument("--predict-chunk-rows", type=int, default=1 << 20)
+    ap.add_argument("--io-threads", type=int, default=16)
     a = ap.parse_args()
     import torch
 
@@ -303,6 +420,10 @@ def main():
         raise SystemExit("bench_score needs a GPU")
     hipops()
     dev = torch.device("cuda", 0)
+    if a.predict_output:
+        print(json.dumps({"bench": "score_predict_output", "repeats": max(2, a.repeats),
+                          "predict_output": bench_predict(a, dev)}), flush=True)
+        return
     out = {"bench": "score", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats,
            "criteo": bench_criteo(a, dev)}
     if not a.skip_rcv1:

@@ -69,8 +69,8 @@ def build_hipops(jobs: int = 8, verbose: bool = False) -> Path:
     src_dir = CSRC / "hip"
     out_dir = BUILD / "hip"
     out_dir.mkdir(parents=True, exist_ok=True)
-    # (textparse.hip / modeltext.hip include the scanners and the formatter they share with
-    # the host runtime)
+    # (textparse.hip / modeltext.hip / scoretext.hip include the scanners and the formatter
+    # they share with the host runtime)
     headers = sorted(src_dir.glob("*.cuh")) + sorted(src_dir.glob("*.h")) + \
         [CSRC / "core" / "textnum.h", CSRC / "core" / "textfmt.h"]
     common = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", str(src_dir),

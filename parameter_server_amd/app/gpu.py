@@ -56,7 +56,11 @@ Flags: ``-app_file``, ``-app_conf`` (appended, reference semantics), ``-num_feat
 (slots per shard; 0 = sized from ``-num_features``), ``-table_growth on`` (the table grows
 on the device before it fills, so the capacity is only where it starts), ``-minibatch`` (rows
 per scored minibatch of the evaluation route, default 65,536: its conf has no solver block
-to take one from)."""
+to take one from), ``-predict_output PATH`` (both scoring routes also write one line per
+example to ``PATH_W<rank>``, formatted on the GPU by ops/scoretext.py: the rank's files in
+``divide_files`` order, unshuffled; lines the parser dropped have no line),
+``-predict_value margin|prob`` (Xw, the default, or sigmoid(Xw)), ``-predict_columns
+score|label,score``."""
 from __future__ import annotations
 
 import os
@@ -94,6 +98,15 @@ def _flags(argv):
     ap.add_argument("-report_steps", "--report_steps", type=int, default=0)
     # rows per scored minibatch of the evaluation route (run_model_evaluation)
     ap.add_argument("-minibatch", "--minibatch", type=int, default=65536)
+    # per-example predictions of the scored files (the evaluation route and the final
+    # validation of a training conf): rank r writes PATH_W<r>, one line per example in the
+    # order of its files, "score" or "label<TAB>score"; margin = Xw (the reference's
+    # `predict` array), prob = sigmoid(Xw)
+    ap.add_argument("-predict_output", "--predict_output", default="")
+    ap.add_argument("-predict_value", "--predict_value", choices=("margin", "prob"),
+                    default="margin")
+    ap.add_argument("-predict_columns", "--predict_columns", choices=("score", "label,score"),
+                    default="score")
     ap.add_argument("-quiet", "--quiet", action="store_true")
     return ap.parse_args(argv)
 
@@ -264,7 +277,9 @@ def run_async_sgd(lm, comm, device, flags, printer=None) -> dict:
 
 def _result_line(r: dict) -> str:
     return (f"auc {r['auc']:.6f} accuracy {r['accuracy']:.6f} examples {r['examples']} "
-            f"loss {r['loss']:.6f}")
+            f"loss {r['loss']:.6f}"
+            + (f" predictions {r['prediction_file']} ({r['prediction_rows']} rows)"
+               if "prediction_file" in r else ""))
 
 
 def _score_files(scorer, data_conf, comm, device, flags, minibatch: int) -> dict:
@@ -288,10 +303,30 @@ def _score_files(scorer, data_conf, comm, device, flags, minibatch: int) -> dict
                           max_lines_per_file=data_conf.max_num_lines_per_file,
                           cache_dir=cache_dir, io_threads=getattr(flags, "io_threads", 16),
                           parser=getattr(flags, "parser", "cpu"))
-    scorer.evaluate(feeder)
+    pred_path = getattr(flags, "predict_output", "")
+    if not pred_path:
+        scorer.evaluate(feeder)
+        pred = None
+    else:
+        from ..ops.scoretext import PredictionWriter
+
+        pred_file = f"{pred_path}_W{rank}"
+        cols = tuple(getattr(flags, "predict_columns", "score").split(","))
+        with PredictionWriter(pred_file, device, columns=cols,
+                              value=getattr(flags, "predict_value", "margin")) as w:
+            scorer.evaluate(feeder, predictions=w)
+            pred = w.close()
     res = scorer.result(comm)
     res.update(rank_examples=feeder.num_examples, h2d_bytes=feeder.bytes_h2d,
                parser=feeder.parser)
+    if pred is not None:
+        if pred["rows"] != feeder.num_examples:
+            raise RuntimeError(f"{pred_file}: {pred['rows']} prediction lines for "
+                               f"{feeder.num_examples} examples")
+        res.update(prediction_file=pred_file, prediction_rows=pred["rows"],
+                   prediction_bytes=pred["bytes"],
+                   prediction_deferred_chunks=pred["deferred_chunks"],
+                   prediction_sources=list(mine))
     return res
 
 

@@ -175,6 +175,22 @@ void register_data(py::module_& m) {
     }
     return py::make_tuple(py::bytes(text), st, len);
   });
+  // The same for bare scores, one prediction-file column (textfmt::put_score): (text of the
+  // kOk scores back to back, no separators, status, length) per f32 bit pattern.
+  m.def("textfmt_scores", [](py::array_t<uint32_t, py::array::c_style> bits) {
+    const py::ssize_t n = bits.size();
+    py::array_t<int32_t> st(n), len(n);
+    std::string text;
+    text.reserve((size_t)n * 12);
+    uint8_t buf[textfmt::kMaxScore];
+    for (py::ssize_t i = 0; i < n; ++i) {
+      int l = 0;
+      st.mutable_data()[i] = textfmt::put_score(bits.data()[i], buf, &l);
+      len.mutable_data()[i] = l;
+      text.append((const char*)buf, (size_t)l);
+    }
+    return py::make_tuple(py::bytes(text), st, len);
+  });
   m.attr("RECORDIO_MAGIC") = kRecordIOMagic;
 }
 

@@ -18,6 +18,10 @@
 // Exact domain: normal f32 with 1e-22 <= |w| < 1e9. Everything else (inf, nan, subnormals,
 // larger, smaller) is kDefer and the caller formats the entry on the host; zero is kSkip
 // (the writers drop zero and NaN weights before they get here; NaN is kDefer).
+//
+// A bare score, one column of a prediction file, is Python's "%.9g" % float(x) over the same
+// domain plus the zeros the model writer never sees: +0 is "0" and -0 is "-0" (dec_score /
+// put_score below).
 #pragma once
 #include "textnum.h"
 
@@ -164,6 +168,33 @@ TEXTNUM_HD int put_weight(const Dec& d, Out* out) {
     out[o++] = (uint8_t)('0' + ax % 10);
   }
   return o;
+}
+
+// A score column: dec_f32 with +-0 inside the domain. A zero is the Dec {n9 = 0, nd = 1,
+// x = 0}, which weight_len / put_weight already turn into "0" / "-0" (one integer digit, no
+// fraction), so the callers need no second case. kOk or kDefer, never kSkip.
+constexpr int kMaxScore = kMaxWeight;
+
+TEXTNUM_HD int dec_score(uint32_t bits, Dec* d) {
+  if ((bits & 0x7fffffffu) == 0) {
+    d->n9 = 0;
+    d->nd = 1;
+    d->x = 0;
+    d->neg = (bits >> 31) != 0;
+    return kOk;
+  }
+  return dec_f32(bits, d);
+}
+
+// The score with these bits into out (room for kMaxScore bytes, no terminator). kOk: *len
+// bytes written; kDefer: nothing written, *len = 0.
+TEXTNUM_HD int put_score(uint32_t bits, uint8_t* out, int* len) {
+  Dec d;
+  *len = 0;
+  const int st = dec_score(bits, &d);
+  if (st != kOk) return st;
+  *len = put_weight(d, out);
+  return kOk;
 }
 
 TEXTNUM_HD int key_len(uint64_t k) {

@@ -2,7 +2,8 @@
 // module, which only calls the binding units' registration hooks (bind_common.h), and the
 // dense unit -- Darlin BCD (bcd.hip), the bf16 GEMMs (gemm.hip, gemm256.hip), embeddings /
 // wide & deep / Adam (embedding.hip) and spmv (spmv.hip). The other kernel families are
-// bound in bind_launch.cpp, bind_table.cpp, bind_tploc.cpp, bind_prep.cpp, bind_linear.cpp.
+// bound in bind_launch.cpp, bind_table.cpp, bind_tploc.cpp, bind_prep.cpp, bind_linear.cpp,
+// bind_scoretext.cpp.
 #include <cmath>
 
 #include "bcd.h"
@@ -662,4 +663,5 @@ PYBIND11_MODULE(_hipops, m) {
   register_prep(m);
   register_linear(m);
   register_dense(m);
+  register_scoretext(m);
 }

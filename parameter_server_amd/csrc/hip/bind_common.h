@@ -32,6 +32,7 @@ void register_tploc(py::module_& m);     // tile / flat localiser, fused step
 void register_prep(py::module_& m);      // localisation, sort / scan / RLE, filters, text
 void register_linear(py::module_& m);    // linear / predict / FM, the generator
 void register_dense(py::module_& m);     // Darlin BCD, GEMMs, embedding, spmv
+void register_scoretext(py::module_& m); // prediction lines
 
 inline hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 

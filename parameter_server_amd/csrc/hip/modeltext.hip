@@ -1,8 +1,9 @@
 // (raw key u64, weight f32) arrays -> key<TAB>weight text on the device (gfx950): the
 // device half of utils/checkpoint.write_text_model, byte for byte. The conversion itself is
 // ../core/textfmt.h (integer arithmetic only, shared with the host); this file lays the
-// entries out. A strict fast path: an entry outside the formatter's exact domain raises the
-// header's deferred count and the caller formats the whole chunk on the host.
+// entries out (the scan and the copy-out are textlayout.cuh, shared with scoretext.hip). A
+// strict fast path: an entry outside the formatter's exact domain raises the header's
+// deferred count and the caller formats the whole chunk on the host.
 //
 // One workgroup owns a fixed block of kMtEntries = 1024 consecutive entries (256 threads x
 // 4 entries). Three launches, no hand-off between workgroups inside a launch:
@@ -26,10 +27,11 @@
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   mt_count_kernel  VGPRs 30, SGPRs 44, ScratchSize 0, LDS    32 B, occupancy 8 waves/SIMD
 //   mt_scan_kernel   VGPRs 40, SGPRs 36, ScratchSize 0, LDS    68 B, occupancy 8
-//   mt_emit_kernel   VGPRs 55, SGPRs 54, ScratchSize 0, LDS 37924 B, occupancy 4 (LDS: four
+//   mt_emit_kernel   VGPRs 55, SGPRs 52, ScratchSize 0, LDS 37924 B, occupancy 4 (LDS: four
 //                    workgroups of four waves a CU)
 #include "modeltext.h"
 #include "common.cuh"
+#include "textlayout.cuh"
 #include "../core/textfmt.h"
 
 #include <stdexcept>
@@ -43,10 +45,6 @@ constexpr int kMtPer = 4;                       // entries per thread
 constexpr int kMtEntries = kMtBlk * kMtPer;     // entries per workgroup
 constexpr int kMtWaves = kMtBlk / kWave;
 constexpr int kMtLds = kMtEntries * textfmt::kMaxEntry + 16;  // + the mod-16 shift
-constexpr int kMtScanBlk = 1024;
-
-// header words (int64)
-enum { H_BYTES, H_DEFER, H_OVER, H_WORDS };
 
 // The text length of entry i (0 when the formatter does not decide it).
 __device__ __forceinline__ int mt_entry(const uint64_t* __restrict__ keys,
@@ -94,54 +92,6 @@ __global__ void __launch_bounds__(kMtBlk) mt_count_kernel(const uint64_t* __rest
   }
 }
 
-// Exclusive scan of one word per thread over a workgroup of kWaves waves. lds: kWaves + 1.
-template <int kWaves>
-__device__ __forceinline__ uint32_t mt_block_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) lds[wid] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t run = 0;
-    for (int w = 0; w < kWaves; ++w) {
-      const uint32_t t = lds[w];
-      lds[w] = run;
-      run += t;
-    }
-    lds[kWaves] = run;
-  }
-  __syncthreads();
-  const uint32_t res = lds[wid] + x - v;
-  *total = lds[kWaves];
-  __syncthreads();
-  return res;
-}
-
-__global__ void __launch_bounds__(kMtScanBlk) mt_scan_kernel(const uint32_t* __restrict__ totals,
-                                                             int64_t nb, int64_t cap,
-                                                             int64_t* __restrict__ offs,
-                                                             unsigned long long* __restrict__ hdr) {
-  __shared__ uint32_t lds[kMtScanBlk / kWave + 1];
-  int64_t run = 0;  // (the same in every thread; a tile is < 2^26 bytes)
-  for (int64_t c = 0; c < nb; c += kMtScanBlk) {
-    const int64_t b = c + threadIdx.x;
-    const uint32_t t = b < nb ? totals[b] : 0u;
-    uint32_t tile;
-    const uint32_t ex = mt_block_scan<kMtScanBlk / kWave>(t, lds, &tile);
-    if (b < nb) offs[b] = run + ex;
-    run += tile;
-  }
-  if (threadIdx.x == 0) {
-    hdr[H_BYTES] = (unsigned long long)run;
-    hdr[H_OVER] = run > cap ? 1ull : 0ull;
-  }
-}
-
 __global__ void __launch_bounds__(kMtBlk) mt_emit_kernel(const uint64_t* __restrict__ keys,
                                                          const uint32_t* __restrict__ wbits,
                                                          int64_t n, const int64_t* __restrict__ offs,
@@ -183,18 +133,7 @@ __global__ void __launch_bounds__(kMtBlk) mt_emit_kernel(const uint64_t* __restr
   }
   __syncthreads();
   if (goff < 0 || goff + (int64_t)total > cap) return;  // (never: the scan checked the sum)
-  // lds byte q <-> out[goff - shift + q]; 16-byte pieces are aligned on both sides
-  uint8_t* base = out + goff - shift;
-  const uint32_t lo = shift, hi = shift + total;
-  const uint32_t npieces = (hi + 15u) >> 4;
-  for (uint32_t pc = threadIdx.x; pc < npieces; pc += kMtBlk) {
-    const uint32_t q = pc << 4;
-    if (q >= lo && q + 16u <= hi) {
-      *reinterpret_cast<uint4*>(base + q) = *reinterpret_cast<const uint4*>(text + q);
-    } else {
-      for (uint32_t b = q < lo ? lo : q; b < q + 16u && b < hi; ++b) base[b] = text[b];
-    }
-  }
+  mt_copy_out<kMtBlk>(text, shift, total, out, goff);
 }
 
 }  // namespace
@@ -202,8 +141,7 @@ __global__ void __launch_bounds__(kMtBlk) mt_emit_kernel(const uint64_t* __restr
 int64_t modeltext_block() { return kMtEntries; }
 int64_t modeltext_max_entry() { return textfmt::kMaxEntry; }
 int64_t modeltext_work_bytes(int64_t n) {
-  const int64_t nb = (n + kMtEntries - 1) / kMtEntries;
-  return nb * 8 + ((nb * 4 + 15) / 16) * 16 + 16;
+  return mt_work_bytes((n + kMtEntries - 1) / kMtEntries);
 }
 
 // Formats n sorted entries into out (cap bytes). hdr: 3 int64 {text bytes, entries the

@@ -97,10 +97,19 @@ class ModelScorer:
         return score(self.table, keys, self.bits, vals=b.vals, labels=b.labels, margins=margins,
                      acc=self.acc, loss=self.loss, B=b.rows, **kw)
 
-    def evaluate(self, feeder, pass_index: int = 0) -> "ModelScorer":
-        """Drain one pass of a ``DeviceFeeder`` (each batch released behind its launch)."""
+    def evaluate(self, feeder, pass_index: int = 0, predictions=None) -> "ModelScorer":
+        """Drain one pass of a ``DeviceFeeder`` (each batch released behind its launch).
+        ``predictions``: a ``PredictionWriter`` (ops/scoretext.py) that takes every batch's
+        margins and labels, in the feeder's row order, before the batch is released; the
+        sums and the histogram are the same with and without one."""
+        if predictions is None:
+            for b in feeder.iter_pass(pass_index):
+                self.score_batch(b)
+                feeder.release(b)
+            return self
         for b in feeder.iter_pass(pass_index):
-            self.score_batch(b)
+            m = self.score_batch(b, margins=True)
+            predictions.append(m, b.labels, rows=b.rows)
             feeder.release(b)
         return self
 
