@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-phase shader-clock durations of the tp bucket kernel (tploc.hip TP_MARK):
-average over workgroups of (mark k - mark k-1), one 65,536 x 39 Criteo minibatch."""
+average over workgroups of (mark k - mark k-1), one 65,536 x 39 Criteo minibatch; then
+the fused forward + backward kernel (FB_MARK) on the compact and on the flat layout."""
 import os
 import sys
 
@@ -43,25 +44,24 @@ loc = L2(keys)
 w = torch.randn(int(loc.uniq.numel()), device="cuda") * 0.01
 met, hist = new_accum("cuda"), torch.zeros(8 * 2 * AUC_BINS, dtype=torch.int32, device="cuda")
 cf = torch.empty(B, device="cuda")
-T = (B * 39 + 8191) // 8192
-prof = torch.zeros(T * 16, dtype=torch.int64, device="cuda")
 
 
-def run():
+def run(name, launch, T):
+    prof = torch.zeros(T * 16, dtype=torch.int64, device="cuda")
     hipops().tp_fb_set_prof(None)
     for _ in range(5):
-        linear_fwd_bwd(loc, w, labels, B=B, width=39, coef=cf, metrics=met, hist=hist)
+        launch()
     torch.cuda.synchronize()
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
     for _ in range(50):
-        linear_fwd_bwd(loc, w, labels, B=B, width=39, coef=cf, metrics=met, hist=hist)
+        launch()
     e.record()
     torch.cuda.synchronize()
     us = s.elapsed_time(e) / 50 * 1e3
     hipops().tp_fb_set_prof(prof)
     for _ in range(3):
-        linear_fwd_bwd(loc, w, labels, B=B, width=39, coef=cf, metrics=met, hist=hist)
+        launch()
     torch.cuda.synchronize()
     hipops().tp_fb_set_prof(None)
     p = prof.view(T, 16).cpu()
@@ -69,14 +69,32 @@ def run():
     d = ph[:, 1:] - ph[:, :-1]
     names = ["loads", "forward", "hist+zero", "atomics", "atomics-drain", "psum"]
     tot = ph[:, 6] - ph[:, 0]
-    print(f"fused: {us:.1f} us per fwd+bwd (+ entry scan); "
+    print(f"{name}: {us:.1f} us per launch; "
           f"tiles {T}: cycles per workgroup mean {tot.mean():.0f} max {tot.max():.0f}")
     for i, n in enumerate(names):
-        print(f"  {n:13s} mean {d[:, i].mean():8.0f}  max {d[:, i].max():8.0f}")
+        print(f"  {n:13s} mean {d[:, i].mean():8.0f}  median {d[:, i].median():8.0f}"
+              f"  max {d[:, i].max():8.0f}")
+    sub = torch.stack([ph[:, 1], p[:, 11].double(), p[:, 12].double(), ph[:, 2]], 1)
+    ds = sub[:, 1:] - sub[:, :-1]  # the forward phase's inner marks
+    for i, n in enumerate(["margins", "row threads", "coefs+max"]):
+        print(f"    {n:11s} mean {ds[:, i].mean():8.0f}  median {ds[:, i].median():8.0f}"
+              f"  max {ds[:, i].max():8.0f}")
     rt0, rt1 = p[:, 8].double(), p[:, 9].double()  # 100 MHz realtime
     t0 = rt0.min()
     print(f"  wall (realtime, us): last start {(rt0.max() - t0) / 100:.1f}, "
           f"last end {(rt1.max() - t0) / 100:.1f}, mean duration {((rt1 - rt0) / 100).mean():.1f}")
 
 
-run()
+run("fused, compact layout (fwd+bwd + entry scan)",
+    lambda: linear_fwd_bwd(loc, w, labels, B=B, width=39, coef=cf, metrics=met, hist=hist),
+    (B * 39 + 8191) // 8192)
+
+# ---- the flat 1-GPU layout (kFlat: weights in tile-entry order, no entry scan) ----
+L3 = Localizer(B * 39, 30, "cuda", mode="tpf")
+f = L3(keys)
+lts = hipops().tpf_tile_log2(B * 39)
+w_ent = torch.randn(f.w_ent.numel(), device="cuda") * 0.01
+run(f"fused, flat layout (tiles of {1 << lts})",
+    lambda: hipops().tp_fwd_bwd(f.rep, f.dcnt, None, B * 39, 39, None, w_ent, labels, B, 2, cf,
+                                met, hist, AUC_BINS, f.psum, None, None, None, None, False),
+    (B * 39 + (1 << lts) - 1) >> lts)

@@ -1156,9 +1156,15 @@ tp_seg_update_kernel(const int32_t* __restrict__ pos_s, const int32_t* __restric
 //     weights wl[e] = w_local[ent_uid[tile + e]] into LDS; an occurrence of a row
 //     cut by the tile boundary resolves its weight through the global entry map
 //     and keeps w * val in its register slot;
-//   forward: margins from registers + LDS, a DPP reduction per lane group, the
-//     leader computes the loss terms (the tile holding a row's first occurrence
-//     owns its coef output, metrics and AUC bin);
+//   forward: margins from registers + LDS, a DPP reduction per lane group into an LDS
+//     row array; then ONE thread per row computes the loss terms (softplus, two expf
+//     and two divides with the AUC bin: once per row, not in all 8 lanes of every
+//     pass) and leaves the row's coef in its label slot, from where the lane groups
+//     read it back (the tile holding a row's first occurrence owns its coef output,
+//     metrics and AUC bin; the tile sums are DPP wave sums, the AUC bins a per-tile
+//     LDS histogram). 65,536 x 39, flat: forward phase 11.9 k -> 7.7 k cycles per
+//     workgroup, kernel 23.5 -> 20.5 us in the pipelined step
+//     (profiles/r7_fused_rows.log);
 //   backward: the same registers add coef * val into per-entry accumulators at rep,
 //     then the per-entry partials psum[tile + e] go to tp_seg_reduce_kernel.
 // The backward accumulates in 64-bit FIXED POINT with integer LDS atomics: on gfx950 a
@@ -1183,6 +1189,20 @@ __device__ __forceinline__ float group8_sum(float m) {
   m += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), 0x141, 0xf, 0xf, false));
   return m;
 }
+// Sum over the wave in lane 63 (DPP row_shr 1/2/4/8, row_bcast:15 / :31, as
+// wave_sum_dpp); the whole wave must be active.
+__device__ __forceinline__ float fb_wave_sum(float v) {
+#define PSAMD_FB_DPP(CTRL, ROWS) \
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xf, false))
+  PSAMD_FB_DPP(0x111, 0xf);
+  PSAMD_FB_DPP(0x112, 0xf);
+  PSAMD_FB_DPP(0x114, 0xf);
+  PSAMD_FB_DPP(0x118, 0xf);
+  PSAMD_FB_DPP(0x142, 0xa);
+  PSAMD_FB_DPP(0x143, 0xc);
+#undef PSAMD_FB_DPP
+  return v;
+}
 
 // Phase marks of the fused kernel (a tuning aid, benchmarks/prof_tp_phases.py): null
 // unless tp_fb_set_prof() installed a buffer of 16 u64 per workgroup.
@@ -1205,13 +1225,16 @@ tp_fwd_bwd_kernel(const uint16_t* __restrict__ rep, const int32_t* __restrict__ 
                   float* __restrict__ psum, int lts) {
   using namespace tp;
   // one 64 KB region: forward = entry weights (f32, [0, 32 KB)) + AUC histogram
-  // ([32 KB, 48 KB)); backward = the entries' fixed-point accumulators (i64)
+  // ([32 KB, 48 KB)) + the rows' margins ([48 KB, 52 KB)); backward = the entries'
+  // fixed-point accumulators (i64)
   __shared__ unsigned long long region[kTile];
-  __shared__ float crow[kFbMaxRows];  // labels of the tile's rows
-  __shared__ float sacc[4];           // tile sums of loss, correct, rows
+  __shared__ float crow[kFbMaxRows];  // labels of the tile's rows, then their coefs
+  __shared__ float sacc[3][kThr / 64];  // loss, correct, rows sums of every row wave
   __shared__ uint32_t smax;           // bits of the tile's largest |coef * val|
   float* const wl = reinterpret_cast<float*>(region);
   uint32_t* const lhist = reinterpret_cast<uint32_t*>(region) + kTile;
+  float* const mrow = reinterpret_cast<float*>(region) + kTile + 2 * kFbMaxBins;
+  static_assert(kTile + 2 * kFbMaxBins + kFbMaxRows <= 2 * kTile, "margins fit the region");
   long long* const acc = reinterpret_cast<long long*>(region);
   constexpr int kRowsPass = kThr / kFbLanes;
   const int t = threadIdx.x, sub = t % kFbLanes, g = t / kFbLanes;
@@ -1245,7 +1268,6 @@ tp_fwd_bwd_kernel(const uint16_t* __restrict__ rep, const int32_t* __restrict__ 
       }
     }
   }
-  if (t < 4) sacc[t] = 0.f;
   if (t == 0) smax = 0u;
   // boundary rows: the outside part of row 0 / row nr-1 (only their lane groups) read
   // their weights through the neighbour tile's entry map; issued first, so the chain
@@ -1276,9 +1298,6 @@ tp_fwd_bwd_kernel(const uint16_t* __restrict__ rep, const int32_t* __restrict__ 
     for (int i = t; i < 2 * nbins; i += kThr) lhist[i] = 0u;
   __syncthreads();
   FB_MARK(1);
-  float loss_acc = 0.f, corr_acc = 0.f, rows_acc = 0.f;
-  float cf[NP];
-  float vmax = 0.f;
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     float m = 0.f;
@@ -1290,13 +1309,22 @@ tp_fwd_bwd_kernel(const uint16_t* __restrict__ rep, const int32_t* __restrict__ 
     }
     m = group8_sum(m);
     const int ri = p * kRowsPass + g;
+    if (sub == 0 && ri < nr) mrow[ri] = m;
+  }
+  __syncthreads();
+  FB_MARK(11);  // (forward = margins | row threads | coefs + tile max)
+  // one thread per row: the loss terms once (not in all 8 lanes of every pass), the
+  // row's coef into its label slot
+  static_assert(NP * kRowsPass <= kThr, "a thread per row of the register passes");
+  float loss_acc = 0.f, corr_acc = 0.f, rows_acc = 0.f;
+  if (const int ri = t; ri < nr) {  // (host: nr <= NP * kRowsPass)
     const int64_t r = r0 + ri;
     float c = 0.f;
-    if (ri < nr && r < B) {
-      const float lab = crow[ri];
+    if (r < B) {
+      const float m = mrow[ri], lab = crow[ri];
       float loss, c2;
       loss_terms(m, lab, loss_type, loss, c, c2);
-      if (sub == 0 && r * width >= base) {  // first occurrence in this tile: the row is ours
+      if (r * width >= base) {  // first occurrence in this tile: the row is ours
         coef_out[r] = c;
         loss_acc += loss;
         corr_acc += ((lab > 0.f) == (m > 0.f)) ? 1.f : 0.f;
@@ -1304,17 +1332,36 @@ tp_fwd_bwd_kernel(const uint16_t* __restrict__ rep, const int32_t* __restrict__ 
         if (hist) atomicAdd(&lhist[auc_bin(m, lab, nbins)], 1u);
       }
     }
-    cf[p] = c;  // every lane of the group holds its row's coef
+    crow[ri] = c;
+  }
+  // tile sums: a DPP sum per row wave into the wave's own slot, the slots summed by
+  // wave 0 below. No float LDS atomics: with a thread per row, 3 ds_add_f32 of 64 lanes
+  // on one address made the forward phase 11.9 k -> 19.8 k cycles (7.8 k with the DPP
+  // sums, profiles/r7_fused_rows.log), and the tile's loss sum has a fixed order.
+  if (metrics && (t & ~63) < nr) {
+    loss_acc = fb_wave_sum(loss_acc);
+    corr_acc = fb_wave_sum(corr_acc);
+    rows_acc = fb_wave_sum(rows_acc);
+    if ((t & 63) == 63) {
+      sacc[0][t >> 6] = loss_acc;
+      sacc[1][t >> 6] = corr_acc;
+      sacc[2][t >> 6] = rows_acc;
+    }
+  }
+  __syncthreads();
+  FB_MARK(12);
+  float cf[NP];  // every lane of a group holds its row's coef
+  float vmax = 0.f;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int ri = p * kRowsPass + g;
+    const float c = ri < nr ? crow[ri] : 0.f;
+    cf[p] = c;
 #pragma unroll
     for (int q = 0; q < PER; ++q)
       if (ce[p][q] < kFbExt) vmax = fmaxf(vmax, fabsf(c * cv[p][q]));
   }
   fx_tile_max(vmax, &smax);
-  if (metrics && rows_acc > 0.f) {  // leader lanes: tile sums (ds_add_f32, 3 per leader)
-    atomicAdd(&sacc[0], loss_acc);
-    atomicAdd(&sacc[1], corr_acc);
-    atomicAdd(&sacc[2], rows_acc);
-  }
   __syncthreads();
   FB_MARK(2);
   if (hist) {  // flush the AUC bins before the region turns into accumulators
@@ -1322,11 +1369,17 @@ tp_fwd_bwd_kernel(const uint16_t* __restrict__ rep, const int32_t* __restrict__ 
     for (int i = t; i < 2 * nbins; i += kThr)
       if (lhist[i]) atomicAdd(&hs[i], lhist[i]);
   }
-  if (metrics && t == 0 && sacc[2] > 0.f) {
-    double* mt = acc_stripe(metrics, acc_stripes);
-    atomicAdd(&mt[0], (double)sacc[0]);
-    atomicAdd(&mt[1], (double)sacc[1]);
-    atomicAdd(&mt[2], (double)sacc[2]);
+  if (metrics && t < 64) {  // wave 0: lane w takes row wave w's sums, one more DPP sum
+    const bool on = t * 64 < nr;
+    const float ls = fb_wave_sum(on ? sacc[0][t] : 0.f);
+    const float cs = fb_wave_sum(on ? sacc[1][t] : 0.f);
+    const float rs = fb_wave_sum(on ? sacc[2][t] : 0.f);
+    if (t == 63 && rs > 0.f) {
+      double* mt = acc_stripe(metrics, acc_stripes);
+      atomicAdd(&mt[0], (double)ls);
+      atomicAdd(&mt[1], (double)cs);
+      atomicAdd(&mt[2], (double)rs);
+    }
   }
   const uint32_t mb = smax;
   __syncthreads();
