@@ -7,7 +7,9 @@ the same minibatches already in HBM.
     python benchmarks/bench_app.py --rows 2000000 --files 8 --minibatch 10000 --kind criteo
 
 kind = criteo: 39 binary features per row (power-law ids, "k:1" LIBSVM, zero-padded ids),
-       rcv1:   5..145 features per row (~75), tf-idf-like values."""
+       rcv1:   5..145 features per row (~75), tf-idf-like values,
+       ctr:    the criteo rows in the slot-grouped SPARSE_BINARY text of the reference's CTR
+               confs, one key per group: "1; 01 00001234; 02 00420000; ...; 39 00000007"."""
 from __future__ import annotations
 
 import argparse
@@ -46,6 +48,30 @@ def _write_criteo_fast(path, keys, y, N):
     out.tofile(path)
 
 
+def _write_ctr_fast(path, keys, y, N):
+    """The same rows as SPARSE_BINARY text (the grammar of data.synthetic.write_text:
+    "label; grp key; grp key ..."), one key per group, groups 01..39, built like
+    _write_criteo_fast (zero-padded ids parse as the same integers)."""
+    per, width = keys.shape
+    nd = len(str(N - 1))
+    tok = nd + 5  # "; gg " digits
+    out = np.empty((per, 2 + width * tok), dtype=np.uint8)
+    out[:, 0] = np.where(y > 0, ord("1"), ord("0"))
+    body = out[:, 1:-1].reshape(per, width, tok)
+    body[:, :, 0] = ord(";")
+    body[:, :, 1] = ord(" ")
+    g = np.arange(1, width + 1)
+    body[:, :, 2] = ord("0") + g // 10
+    body[:, :, 3] = ord("0") + g % 10
+    body[:, :, 4] = ord(" ")
+    k = keys.copy()
+    for p in range(nd - 1, -1, -1):
+        body[:, :, 5 + p] = ord("0") + (k % 10)
+        k //= 10
+    out[:, -1] = ord("\n")
+    out.tofile(path)
+
+
 def _breakdown(tr, d, a, steps, cache):
     """Where a cached run's time goes: the feeder alone (pread -> pinned -> HBM, no
     training) and the trainer alone (the same step count on one HBM-resident minibatch)."""
@@ -55,7 +81,7 @@ def _breakdown(tr, d, a, steps, cache):
 
     dev = torch.device("cuda")
     files = sorted(os.path.join(d, f) for f in os.listdir(d) if f.startswith("part-"))
-    f = DeviceFeeder(files, "LIBSVM", a.minibatch, tr.max_nnz, dev, num_features=10 ** 8,
+    f = DeviceFeeder(files, _text_format(a.kind), a.minibatch, tr.max_nnz, dev, num_features=10 ** 8,
                      cache_dir=cache, io_threads=a.io_threads)
     torch.cuda.synchronize()
     t0 = time.time()
@@ -71,7 +97,7 @@ def _breakdown(tr, d, a, steps, cache):
     feed_s = time.time() - t0
     out = {"source": "breakdown", "feeder_only_examples_per_s": ex / feed_s,
            "feeder_only_h2d_gb_per_s": f.bytes_h2d / feed_s / 1e9, "feeder_batches": n}
-    if last is not None and a.kind == "criteo":
+    if last is not None and a.kind in ("criteo", "ctr"):
         keys, labels = last
         for _ in range(3):
             tr.step(keys, labels, width=39)
@@ -85,15 +111,20 @@ def _breakdown(tr, d, a, steps, cache):
     return out
 
 
+def _text_format(kind):
+    return "SPARSE_BINARY" if kind == "ctr" else "LIBSVM"
+
+
 def write_files(d, kind, rows, files, seed=0, N=10 ** 8):
     rng = np.random.default_rng(seed)
     per = rows // files
     for f in range(files):
         print(f"[bench_app] writing file {f + 1} / {files}", file=sys.stderr, flush=True)
-        if kind == "criteo":
+        if kind in ("criteo", "ctr"):
             keys = np.sort((N * rng.random((per, 39)) ** 4).astype(np.int64), axis=1)
             y = np.where(rng.random(per) < 0.3, 1, -1)
-            _write_criteo_fast(os.path.join(d, f"part-{f:03d}"), keys, y, N)
+            write = _write_criteo_fast if kind == "criteo" else _write_ctr_fast
+            write(os.path.join(d, f"part-{f:03d}"), keys, y, N)
             continue
         if kind == "criteo_slow":
             w = np.full(per, 39)
@@ -123,7 +154,7 @@ def main():
     ap.add_argument("--rows", type=int, default=2_000_000)
     ap.add_argument("--files", type=int, default=8)
     ap.add_argument("--minibatch", type=int, default=10000)
-    ap.add_argument("--kind", default="criteo", choices=["criteo", "criteo_slow", "rcv1"])
+    ap.add_argument("--kind", default="criteo", choices=["criteo", "criteo_slow", "rcv1", "ctr"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--dir", default="")
     ap.add_argument("--cache", type=int, default=1,
@@ -151,7 +182,7 @@ def main():
     conf = os.path.join(d, "online.conf")
     with open(conf, "w") as f:
         f.write(f"""linear_method {{
-training_data {{ format: TEXT text: LIBSVM file: "{d}/part.*" }}
+training_data {{ format: TEXT text: {_text_format(a.kind)} file: "{d}/part.*" }}
 loss {{ type: LOGIT }}
 penalty {{ type: L1 lambda: 10 lambda: 1 }}
 learning_rate {{ type: DECAY alpha: 0.01 beta: 10 }}

@@ -90,8 +90,9 @@ def _flags(argv):
     # (Criteo-shaped 8 M rows, B = 65,536: 8 threads 52-64 M ex/s, 16 threads 86 M,
     # profiles/r6_app_cache.log)
     ap.add_argument("-io_threads", "--io_threads", type=int, default=16)
-    # text parser of the file-fed path: "cpu" (C++ parser threads), "gpu" (LIBSVM / CRITEO
-    # text parsed by HIP kernels, data/feeder.py), "auto" (gpu where it applies)
+    # text parser of the file-fed path and of Darlin's load: "cpu" (C++ parser threads),
+    # "gpu" (LIBSVM / CRITEO / SPARSE_BINARY / SPARSE text parsed by HIP kernels,
+    # data/feeder.py, data/slot_reader.py), "auto" (gpu where it applies)
     ap.add_argument("-parser", "--parser", choices=("cpu", "gpu", "auto"), default="cpu")
     # progress lines every this many steps when the step count is agreed up front (a
     # fully cached multi-rank run); 0 = 20 lines per run
@@ -386,7 +387,8 @@ def run_darlin(lm, comm, device, flags, printer=None) -> dict:
                         cache_prefix=(cache.file[0] if cache is not None and cache.has("file")
                                       else None), ignore_slot=td.ignore_feature_group,
                         hadoop_home=td.hdfs.home if td.has("hdfs") else "",
-                        nthreads=flags.num_threads)
+                        nthreads=flags.num_threads, parser=getattr(flags, "parser", "cpu"),
+                        device=device)
     data = reader.read()
     cfg = DarlinConfig.from_lm(lm, seed=flags.seed)
     t0 = time.time()

@@ -25,7 +25,8 @@ device slots; ``release(batch)`` after the step that reads it was issued):
   a multi-rank app agrees on its step count once instead of every step.
 
 The text source has two parsers (``parser=``). ``"cpu"`` (the default) is the path above.
-``"gpu"`` parses LIBSVM / CRITEO text on the device (ops/textparse.py, textparse.hip):
+``"gpu"`` parses LIBSVM / CRITEO text (ops/textparse.py, textparse.hip) and the slot-grouped
+SPARSE_BINARY / SPARSE text of the CTR confs (ops/pstext.py, pstext.hip) on the device:
 reader threads read each file straight into pinned chunk buffers of ``chunk_bytes``, cut at
 the last newline; a chunk is copied to HBM on the copy stream and parsed on a parse stream
 into one of a ring of device output buffers; minibatches are slices of the parsed chunk
@@ -53,7 +54,7 @@ import torch
 
 from . import TEXT_FORMATS, ExampleBatch, StreamReader, read_file
 from . import bincache
-from ..ops import textparse
+from ..ops import pstext, textparse
 
 
 @dataclass
@@ -163,7 +164,10 @@ class DeviceFeeder:
         self._fmt_id = TEXT_FORMATS.get(fmt, 0) if isinstance(fmt, str) else int(fmt)
         # the parser in use: the device parser needs a GPU, a format it knows and whole files
         self.parser = "gpu" if (parser != "cpu" and self.gpu and max_lines_per_file <= 0
-                                and textparse.supported(self._fmt_id)) else "cpu"
+                                and (textparse.supported(self._fmt_id)
+                                     # (group heads are validated only when slots are kept)
+                                     or (pstext.supported(self._fmt_id) and ignore_slot))
+                                ) else "cpu"
         self.chunk_bytes = max(1024, int(chunk_bytes))
         self.text_chunks = 0      # chunks of text handed to the device parser
         self.deferred_chunks = 0  # of them: parsed by the CPU parser after all
@@ -468,7 +472,9 @@ class DeviceFeeder:
                     it = ("chunk", i, n, f, d, ev)
                 return it
 
-            libsvm = self._fmt_id == TEXT_FORMATS["LIBSVM"]
+            # (the formats whose chunks keep a value per feature; the others are binary)
+            valued = self._fmt_id in (TEXT_FORMATS["LIBSVM"], TEXT_FORMATS["SPARSE"])
+            grouped = pstext.supported(self._fmt_id)
             carry = None     # rows parsed but not yet cut into a minibatch
             pieces = []      # host copies of the current file's arrays (cache_dir)
             nxt = fetch()
@@ -493,7 +499,7 @@ class DeviceFeeder:
                         st.grow(r0 + 1, n0 + 1)
                         st.labels[:r0].copy_(P.labels[a:a + r0])
                         st.keys[:n0].copy_(P.keys[na:na + n0])
-                        if libsvm:
+                        if valued:
                             st.vals[:n0].copy_(P.vals[na:na + n0])
                         textparse.rebase_row_ptr(P.row_ptr[a:a + r0 + 1], st.row_ptr, r0 + 1, na)
                         P.unhold()
@@ -501,9 +507,14 @@ class DeviceFeeder:
                     if cur[0] == "chunk":
                         _, i, n, f, d, ev = cur
                         ps.wait_event(ev)
-                        res = textparse.parse_text_device(d, self._fmt_id, self.num_features,
-                                                          out=st, row0=r0, nnz0=n0, n=n,
-                                                          host=tp["pin"][i])
+                        if grouped:  # (minibatches carry no slot ids: the group heads are not read)
+                            res = pstext.parse_ps_text_device(
+                                d, self._fmt_id, self.num_features, ignore_slot=True, out=st,
+                                row0=r0, nnz0=n0, n=n, host=tp["pin"][i])
+                        else:
+                            res = textparse.parse_text_device(
+                                d, self._fmt_id, self.num_features, out=st, row0=r0, nnz0=n0,
+                                n=n, host=tp["pin"][i])
                         free_pin.put(i)
                     else:  # a line longer than a chunk: the CPU parser's
                         n = len(cur[1])
@@ -521,8 +532,8 @@ class DeviceFeeder:
                         W = res.width if res.width == carry["W"] else 0
                     rp = None if W else st.row_ptr[:Rn + 1].cpu().numpy()
                     if self.cache_dir:
-                        pieces.append(self._host_piece(st, res, r0, n0, W, rp, libsvm))
-                    nonunit = libsvm and (res.vals is not None or
+                        pieces.append(self._host_piece(st, res, r0, n0, W, rp, valued))
+                    nonunit = valued and (res.vals is not None or
                                           (carry is not None and carry["nonunit"]))
                     carry = self._cut_chunk(st, 0, Rn, N, W, rp, nonunit, False, out_q, ps)
             if carry is not None:  # the rows left at the end of the pass
@@ -603,13 +614,13 @@ class DeviceFeeder:
             out_q.put(b)
         return left
 
-    def _host_piece(self, st, res, r0, n0, W, rp, libsvm):
+    def _host_piece(self, st, res, r0, n0, W, rp, valued):
         """Host copies of the rows a chunk added (for the file's binary cache)."""
         rows, nnz = res.rows, res.nnz
         lrp = np.arange(0, (rows + 1) * W, W, dtype=np.int64) if W else rp[r0:r0 + rows + 1] - n0
         return (st.labels[r0:r0 + rows].cpu().numpy(), lrp,
                 st.keys[n0:n0 + nnz].cpu().numpy().view(np.uint64),
-                st.vals[n0:n0 + nnz].cpu().numpy() if libsvm else None)
+                st.vals[n0:n0 + nnz].cpu().numpy() if valued else None)
 
     def _write_cache_pieces(self, f: str, pieces):
         """One file's parsed arrays as its binary cache (as StreamReader._write_cache)."""

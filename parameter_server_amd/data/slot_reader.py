@@ -11,6 +11,13 @@ Here files are parsed by the C++ runtime (``_pscore.parse_text``), the cache is
 ``.npy`` arrays (loaded with ``allow_pickle=False``) plus a JSON ``.info``, and
 slot info follows the reference ``InfoParser`` (src/data/info_parser.cc:10-48):
 ``max_key`` is exclusive (max + 1), label slot 0 has range [0, 1).
+
+``parser="gpu"`` with a GPU ``device`` parses SPARSE_BINARY / SPARSE files on the device on
+a cache miss (ops/pstext.py: <= 32 MiB chunks cut at a newline, slot ids included); the
+arrays come back as an ``ExampleBatch`` and go through the same split and cache. Other
+formats, ``.gz`` / ``hdfs://`` paths and CPU devices stay on the host parser, and so does
+``parser="auto"``: the split by slot on the host bounds the load, and the device route
+measured no faster than the host route.
 """
 from __future__ import annotations
 
@@ -21,7 +28,9 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import merge_example_info, parse_text, read_file
+from . import ExampleBatch, merge_example_info, parse_text, read_file
+
+_CHUNK = 32 << 20  # bytes of text per device parse
 
 
 @dataclass
@@ -90,7 +99,10 @@ class SlotData:
 
 class SlotReader:
     def __init__(self, files, fmt: str = "LIBSVM", cache_prefix: str | None = None,
-                 ignore_slot: bool = False, hadoop_home: str = "", nthreads: int = 4):
+                 ignore_slot: bool = False, hadoop_home: str = "", nthreads: int = 4,
+                 parser: str = "cpu", device=None):
+        if parser not in ("cpu", "gpu", "auto"):
+            raise ValueError(f"parser must be 'cpu', 'gpu' or 'auto', not {parser!r}")
         self.files = list(files)
         self.fmt = fmt
         self.cache = cache_prefix
@@ -98,15 +110,23 @@ class SlotReader:
         self.hadoop = hadoop_home
         self.nthreads = max(1, nthreads)
         self.hit_cache = 0
+        self.device = device
+        # the parser in use: the device parser needs a GPU and a format it knows. "auto" stays
+        # on the host: the load is bound by the split by slot on the host, and the device
+        # route measured no faster (benchmarks/bench_slotreader.py)
+        self.parser = "gpu" if (parser == "gpu" and _is_gpu_device(device)
+                                and _ps_supported(fmt)) else "cpu"
+        self.deferred_chunks = 0  # device route: chunks the host parser took after all
 
     @staticmethod
-    def from_config(data_conf, cache_conf=None, nthreads: int = 4) -> "SlotReader":
+    def from_config(data_conf, cache_conf=None, nthreads: int = 4, parser: str = "cpu",
+                    device=None) -> "SlotReader":
         cache = None
         if cache_conf is not None and cache_conf.has("file") and cache_conf.file:
             cache = cache_conf.file[0]
         hadoop = data_conf.hdfs.home if data_conf.has("hdfs") else ""
         return SlotReader(list(data_conf.file), data_conf.text, cache,
-                          data_conf.ignore_feature_group, hadoop, nthreads)
+                          data_conf.ignore_feature_group, hadoop, nthreads, parser, device)
 
     def _cache_name(self, path: str) -> str:
         return f"{self.cache}{os.path.basename(path)}"
@@ -152,18 +172,75 @@ class SlotReader:
         if sd is not None:
             self.hit_cache += 1
             return sd
-        batch = parse_text(read_file(path, self.hadoop), self.fmt, ignore_slot=self.ignore_slot)
+        if self.parser == "gpu" and not self.hadoop and not path.startswith("hdfs://") \
+                and not path.endswith(".gz"):
+            batch = self._parse_device(path)
+        else:
+            batch = parse_text(read_file(path, self.hadoop), self.fmt,
+                               ignore_slot=self.ignore_slot)
         sd = SlotData.from_batch(batch)
         self._store_cache(path, sd)
         return sd
 
+    def _parse_device(self, path: str) -> ExampleBatch:
+        """One plain file through the device parser, chunk by chunk, as an ExampleBatch."""
+        import torch
+
+        from ..ops.pstext import parse_ps_text_device
+
+        with open(path, "rb") as f:
+            raw = f.read()
+        parts, a = [], 0
+        while a < len(raw):
+            b = len(raw)
+            if b - a > _CHUNK:  # cut behind the chunk's last newline (a longer line: whole)
+                k = raw.rfind(b"\n", a, a + _CHUNK)
+                b = k + 1 if k >= 0 else (raw.find(b"\n", a + _CHUNK) + 1 or len(raw))
+            host = raw[a:b]
+            with torch.cuda.device(self.device):
+                res = parse_ps_text_device(
+                    torch.frombuffer(bytearray(host), dtype=torch.uint8).to(self.device), self.fmt,
+                    ignore_slot=self.ignore_slot, host=host)
+                self.deferred_chunks += bool(res.deferred)
+                n = res.nnz
+                # (the host parser files every feature under slot 1 when slots are ignored)
+                slots = np.ones(n, np.int32) if res.slots is None else res.slots.cpu().numpy()
+                parts.append(ExampleBatch(
+                    res.labels.cpu().numpy(), res.row_ptr.cpu().numpy(),
+                    res.keys.cpu().numpy().view(np.uint64),
+                    np.ones(n, np.float32) if res.valued and res.vals is None else
+                    (None if res.vals is None else res.vals.cpu().numpy()), slots))
+            a = b
+        if not parts:
+            return parse_text(raw, self.fmt, ignore_slot=self.ignore_slot)
+        if any(p.vals is not None and bool((p.vals != 1).any()) for p in parts):
+            return ExampleBatch.concat(parts)
+        for p in parts:  # (every value is 1: binary features, as the host parser has it)
+            p.vals = None
+        return ExampleBatch.concat(parts)
+
     def read(self) -> SlotData:
         self.hit_cache = 0
+        self.deferred_chunks = 0
         with ThreadPoolExecutor(self.nthreads) as pool:
             parts = list(pool.map(self._read_one, self.files))
         if not parts:
             return SlotData(labels=np.zeros(0, np.float32))
         return SlotData.concat(parts)
+
+
+def _is_gpu_device(device) -> bool:
+    if device is None:
+        return False
+    import torch
+
+    return torch.device(device).type == "cuda"
+
+
+def _ps_supported(fmt) -> bool:
+    from ..ops.pstext import supported
+
+    return supported(fmt)
 
 
 def _jsonable(info: dict) -> dict:

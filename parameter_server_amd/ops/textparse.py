@@ -20,6 +20,8 @@ import torch
 from .native import hipops, is_gpu
 
 _DEVICE_FORMATS = {"LIBSVM": 5, "CRITEO": 8}
+# formats whose parsed chunks keep their values in the ``vals`` buffer (ones included)
+_VALUED_FORMATS = (5, 2)  # LIBSVM, SPARSE (ops/pstext.py)
 # header words of textparse.hip
 H_ROWS, H_NNZ, H_MINW, H_MAXW, H_NONUNIT, H_BAD, H_DEFER, H_CAP = range(8)
 MAX_CHUNK = 1 << 30
@@ -41,7 +43,9 @@ def _fmt_id(fmt) -> int:
 class TextParseBuffers:
     """Caller-owned outputs of the device parser: ``labels`` f32 [cap_rows], ``row_ptr``
     i64 [cap_rows + 1], ``keys`` i64 [cap_nnz] (u64 bit patterns), ``vals`` f32 [cap_nnz],
-    the header and the kernels' work space."""
+    the header and the kernels' work space. ``slots`` i32 [cap_nnz] (the feature group of
+    every entry, ops/pstext.py) is allocated on first use and then grown and carried like
+    ``keys``."""
 
     def __init__(self, cap_rows: int, cap_nnz: int, device, text_bytes: int = 0):
         dev = torch.device(device)
@@ -50,6 +54,7 @@ class TextParseBuffers:
         self.row_ptr = torch.zeros(max(1, cap_rows) + 1, dtype=torch.int64, device=dev)
         self.keys = torch.empty(max(1, cap_nnz), dtype=torch.int64, device=dev)
         self.vals = torch.empty(max(1, cap_nnz), dtype=torch.float32, device=dev)
+        self.slots = None
         self.hdr = torch.zeros(8, dtype=torch.int32, device=dev)
         self.work = None
         if text_bytes and dev.type == "cuda":
@@ -63,10 +68,15 @@ class TextParseBuffers:
     def cap_nnz(self) -> int:
         return self.keys.numel()
 
-    def reserve_work(self, n: int):
-        need = int(hipops().textparse_work_words(n))
+    def reserve_work(self, n: int, ps: bool = False):
+        """Work space for ``n`` bytes of text (``ps``: for the parser of ops/pstext.py)."""
+        need = int(hipops().pstext_work_words(n) if ps else hipops().textparse_work_words(n))
         if self.work is None or self.work.numel() < need:
             self.work = torch.empty(need, dtype=torch.int32, device=self.device)
+
+    def reserve_slots(self):
+        if self.slots is None:
+            self.slots = torch.empty(self.cap_nnz, dtype=torch.int32, device=self.device)
 
     def grow(self, rows: int, nnz: int, keep_rows: int = 0, keep_nnz: int = 0):
         """Room for ``rows`` / ``nnz`` in new tensors (earlier views stay valid); the first
@@ -82,6 +92,10 @@ class TextParseBuffers:
             v = torch.empty(nnz, dtype=torch.float32, device=self.device)
             k[:keep_nnz].copy_(self.keys[:keep_nnz])
             v[:keep_nnz].copy_(self.vals[:keep_nnz])
+            if self.slots is not None:
+                sl = torch.empty(nnz, dtype=torch.int32, device=self.device)
+                sl[:keep_nnz].copy_(self.slots[:keep_nnz])
+                self.slots = sl
             self.keys, self.vals = k, v
 
 
@@ -98,6 +112,7 @@ class ParsedText:
     deferred: bool                # the host parser produced the arrays
     valued: bool = False          # ``vals`` buffer region holds the values (ones included)
     out: TextParseBuffers | None = None
+    slots: torch.Tensor | None = None  # i32 [nnz]: feature group per entry (ops/pstext.py)
 
 
 def _as_bytes(buf, n) -> bytes:
@@ -119,17 +134,21 @@ def _width_of(rp: np.ndarray) -> int:
     return int(w[0]) if w[0] > 0 and bool((w == w[0]).all()) else 0
 
 
-def _store_host(b, out: TextParseBuffers, row0: int, nnz0: int, fmt_id: int, deferred: bool):
+def _store_host(b, out: TextParseBuffers, row0: int, nnz0: int, fmt_id: int, deferred: bool,
+                slots: bool = False):
     """Upload a host-parsed batch behind row0 / nnz0 (the buffers grow when it does not
-    fit: a chunk the device declined may be denser than its capacity)."""
+    fit: a chunk the device declined may be denser than its capacity). ``slots``: the
+    batch's slot ids as well."""
     rows, nnz = b.rows, b.nnz
+    if slots:
+        out.reserve_slots()
     out.grow(row0 + rows, nnz0 + nnz, row0, nnz0)
     rp = np.asarray(b.row_ptr, dtype=np.int64)
     out.labels[row0:row0 + rows].copy_(torch.from_numpy(np.ascontiguousarray(b.labels)))
     out.row_ptr[row0:row0 + rows + 1].copy_(torch.from_numpy(rp + nnz0))
     out.keys[nnz0:nnz0 + nnz].copy_(
         torch.from_numpy(np.ascontiguousarray(b.keys).view(np.int64)))
-    valued = fmt_id == _DEVICE_FORMATS["LIBSVM"] or b.vals is not None
+    valued = fmt_id in _VALUED_FORMATS or b.vals is not None
     if b.vals is not None:
         out.vals[nnz0:nnz0 + nnz].copy_(torch.from_numpy(np.ascontiguousarray(b.vals)))
     elif valued:
@@ -137,7 +156,15 @@ def _store_host(b, out: TextParseBuffers, row0: int, nnz0: int, fmt_id: int, def
     return ParsedText(out.labels[row0:row0 + rows], out.row_ptr[row0:row0 + rows + 1],
                       out.keys[nnz0:nnz0 + nnz],
                       None if b.vals is None else out.vals[nnz0:nnz0 + nnz], rows, nnz,
-                      int(b.info.get("bad_lines", 0)), _width_of(rp), deferred, valued, out)
+                      int(b.info.get("bad_lines", 0)), _width_of(rp), deferred, valued, out,
+                      _store_slots(b, out, nnz0) if slots else None)
+
+
+def _store_slots(b, out: TextParseBuffers, nnz0: int):
+    nnz = b.nnz
+    out.slots[nnz0:nnz0 + nnz].copy_(
+        torch.from_numpy(np.ascontiguousarray(b.slots, dtype=np.int32)))
+    return out.slots[nnz0:nnz0 + nnz]
 
 
 def parse_text_device(buf, fmt, hash_mod: int = 0, *, out: TextParseBuffers | None = None,
