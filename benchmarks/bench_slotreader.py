@@ -1,8 +1,16 @@
 """Darlin's load: ``SlotReader.read()`` over slot-grouped SPARSE_BINARY files, the host route
-(C++ parser) against the device route (pstext.hip), alternating in one process on the same
-files, no cache. Prints one JSON line.
+(C++ parser, split by slot on the host) against the device routes (pstext.hip, then the split
+on the host, on the device (slotsplit.hip), or on the device with the groups left there),
+alternating in one process on the same files, no cache. Prints one JSON line.
 
-    python benchmarks/bench_slotreader.py --rows 2000000 --files 8 --parser cpu,gpu,cpu,gpu
+    python benchmarks/bench_slotreader.py --rows 2000000 --files 8 --warmup 1 \\
+        --parser cpu,gpu,gpu,gpu,cpu,gpu,gpu,gpu \\
+        --split host,host,device,resident,host,host,device,resident
+
+``--split`` pairs with ``--parser`` entry by entry (a shorter list repeats its last entry):
+``host``, ``device``, or ``resident`` (``device`` with ``resident=True``). ``--warmup N``
+reads every distinct route N times first, untimed. ``--csc`` also builds a ``DarlinTrainer``
+from resident and from host-route data and reports its ``prep_times`` on a second line.
 """
 from __future__ import annotations
 
@@ -23,6 +31,9 @@ def main():
     ap.add_argument("--files", type=int, default=8)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--parser", default="cpu,gpu,cpu,gpu")
+    ap.add_argument("--split", default="host")
+    ap.add_argument("--warmup", type=int, default=0)
+    ap.add_argument("--csc", action="store_true")
     ap.add_argument("--dir", default="")
     a = ap.parse_args()
     import torch
@@ -35,16 +46,36 @@ def main():
     write_files(d, "ctr", a.rows, a.files)
     files = sorted(os.path.join(d, f) for f in os.listdir(d) if f.startswith("part-"))
     mb = sum(os.path.getsize(f) for f in files) / 1e6
-    runs = []
-    for parser in a.parser.split(","):
-        r = SlotReader(files, "SPARSE_BINARY", nthreads=a.threads, parser=parser, device="cuda")
+    parsers = a.parser.split(",")
+    splits = a.split.split(",")
+    splits += [splits[-1]] * (len(parsers) - len(splits))
+    routes = list(zip(parsers, splits))
+
+    def reader(parser, split):
+        return SlotReader(files, "SPARSE_BINARY", nthreads=a.threads, parser=parser, device="cuda",
+                          split="host" if split == "host" else "device",
+                          resident=split == "resident")
+
+    def read(parser, split):
+        r = reader(parser, split)
         t0 = time.time()
         sd = r.read()
-        dt = time.time() - t0
-        runs.append({"parser": r.parser, "read_s": round(dt, 3), "rows": sd.rows,
+        torch.cuda.synchronize()
+        return r, sd, time.time() - t0
+
+    for _ in range(a.warmup):
+        for parser, split in dict.fromkeys(routes):
+            read(parser, split)
+    runs = []
+    for parser, split in routes:
+        r, sd, dt = read(parser, split)
+        runs.append({"parser": r.parser, "split": r.split, "resident": r.resident,
+                     "read_s": round(dt, 3), "rows": sd.rows,
                      "groups": len(sd.groups), "deferred_chunks": r.deferred_chunks,
+                     "split_deferred_chunks": r.split_deferred_chunks,
                      "examples_per_s": sd.rows / dt, "text_mb_per_s": mb / dt})
-        print(f"[bench_slotreader] {r.parser}: {dt:.2f} s", file=sys.stderr, flush=True)
+        print(f"[bench_slotreader] {r.parser} / {r.split}{' resident' if r.resident else ''}: "
+              f"{dt:.2f} s", file=sys.stderr, flush=True)
         del sd
     # where the time goes: the parse alone of one file on either route, and the split by slot
     raw = open(files[0], "rb").read()
@@ -60,11 +91,71 @@ def main():
     t0 = time.time()
     SlotData.from_batch(b)
     t_split = time.time() - t0
-    print(json.dumps({"bench": "slot_reader", "files": a.files, "text_mb": round(mb, 1),
-                      "threads": a.threads, "runs": runs,
-                      "one_file": {"rows": b.rows, "host_parse_s": round(t_host, 3),
-                                   "device_parse_and_copy_back_s": round(t_dev, 3),
-                                   "split_by_slot_s": round(t_split, 3)}}), flush=True)
+    one = {"rows": b.rows, "host_parse_s": round(t_host, 3),
+           "device_parse_and_copy_back_s": round(t_dev, 3), "split_by_slot_s": round(t_split, 3)}
+    if any(s != "host" for s in splits):
+        one.update(_device_split_times(files[0]))
+    out = {"bench": "slot_reader", "files": a.files, "text_mb": round(mb, 1),
+           "threads": a.threads, "runs": runs, "one_file": one}
+    print(json.dumps(out), flush=True)
+    if a.csc:  # (a line of its own: the trainers take longer than everything above)
+        print(json.dumps({"bench": "slot_reader_darlin_prep", "rows": a.rows,
+                          "prep_times": _csc_times(read)}), flush=True)
+
+
+def _device_split_times(path: str) -> dict:
+    """One file on the device: the parse alone (nothing copied back), the split of the parsed
+    chunks alone, and the whole resident read of the file."""
+    import torch
+
+    from parameter_server_amd.data.slot_reader import SlotReader
+    from parameter_server_amd.ops.pstext import parse_ps_text_device
+    from parameter_server_amd.ops.slotsplit import split_by_slot
+
+    def parse():
+        with open(path, "rb") as f:
+            chunks = SlotReader._text_chunks(f.read())
+        return [parse_ps_text_device(torch.frombuffer(bytearray(c), dtype=torch.uint8).to("cuda"),
+                                     "SPARSE_BINARY", ignore_slot=False, host=c) for c in chunks]
+
+    def split(parsed):
+        return [split_by_slot(None, p.row_ptr, p.keys, p.vals, p.slots) for p in parsed]
+
+    split(parse())
+    torch.cuda.synchronize()
+    t0 = time.time()
+    parsed = parse()
+    torch.cuda.synchronize()
+    t1 = time.time()
+    sp = split(parsed)
+    torch.cuda.synchronize()
+    t2 = time.time()
+    r = SlotReader([path], "SPARSE_BINARY", parser="gpu", split="device", resident=True,
+                   device="cuda")
+    r.read()
+    torch.cuda.synchronize()
+    return {"chunks": len(parsed), "device_parse_s": round(t1 - t0, 4),
+            "device_split_s": round(t2 - t1, 4), "split_deferred_chunks": sum(s.deferred for s in sp),
+            "resident_read_s": round(time.time() - t2, 4)}
+
+
+def _csc_times(read) -> dict:
+    """``DarlinTrainer``'s preprocessing from resident data and from the host route's."""
+    import torch
+
+    from parameter_server_amd.models.darlin import DarlinConfig, DarlinTrainer
+
+    out = {}
+    cfg = DarlinConfig(l1=1.0, max_pass=1, seed=0)
+    for name, route in (("host_data", ("cpu", "host")), ("resident_data", ("gpu", "resident")),
+                        ("host_data_again", ("cpu", "host")),
+                        ("resident_data_again", ("gpu", "resident"))):
+        _, sd, _ = read(*route)
+        tr = DarlinTrainer(sd, cfg, device=torch.device("cuda"))
+        out[name] = {k: round(v, 4) for k, v in tr.prep_times.items()}
+        del tr, sd
+        torch.cuda.empty_cache()
+    return out
 
 
 if __name__ == "__main__":

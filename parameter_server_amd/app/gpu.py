@@ -28,7 +28,11 @@ torchrun rank is one GPU = a colocated worker + server shard:
   fixed-width path; anything else the CSR (``row_ptr`` + ``vals``) path. With several
   ranks a rank whose files ran out keeps joining the exchanges with key-less steps
   (it still owns a shard) until every rank is done.
-* ``darlin`` -> ``DarlinTrainer`` (models/darlin.py) through ``DarlinConfig.from_lm``.
+* ``darlin`` -> ``DarlinTrainer`` (models/darlin.py) through ``DarlinConfig.from_lm``. The
+  rank's files are loaded by ``SlotReader``; with ``-parser gpu -slot_split device`` they are
+  parsed and split by feature group on the device and, when the trainer runs on the GPU,
+  stay there (the summary reports ``parser``, ``slot_split``, ``deferred_chunks`` and
+  ``split_deferred_chunks``).
 * progress: the reference's ``sec examples loss auc accuracy |w|_0 updt ratio`` line
   (ISGDScheduler::showProgress, sgd.h:45-80) every ``report_interval`` seconds, and the
   Darlin tables (darlin.h:136-156).
@@ -60,7 +64,8 @@ to take one from), ``-predict_output PATH`` (both scoring routes also write one 
 example to ``PATH_W<rank>``, formatted on the GPU by ops/scoretext.py: the rank's files in
 ``divide_files`` order, unshuffled; lines the parser dropped have no line),
 ``-predict_value margin|prob`` (Xw, the default, or sigmoid(Xw)), ``-predict_columns
-score|label,score``."""
+score|label,score``, ``-slot_split host|device`` (Darlin's load: where the examples are split
+by feature group; ``device`` takes effect behind ``-parser gpu``)."""
 from __future__ import annotations
 
 import os
@@ -94,6 +99,10 @@ def _flags(argv):
     # "gpu" (LIBSVM / CRITEO / SPARSE_BINARY / SPARSE text parsed by HIP kernels,
     # data/feeder.py, data/slot_reader.py), "auto" (gpu where it applies)
     ap.add_argument("-parser", "--parser", choices=("cpu", "gpu", "auto"), default="cpu")
+    # Darlin's load: where the parsed examples are split by feature group. "device" (behind
+    # -parser gpu only) splits them by HIP kernels and, when the trainer runs on the GPU,
+    # hands it the groups as device tensors (data/slot_reader.py, ops/slotsplit.py)
+    ap.add_argument("-slot_split", "--slot_split", choices=("host", "device"), default="host")
     # progress lines every this many steps when the step count is agreed up front (a
     # fully cached multi-rank run); 0 = 20 lines per run
     ap.add_argument("-report_steps", "--report_steps", type=int, default=0)
@@ -388,7 +397,8 @@ def run_darlin(lm, comm, device, flags, printer=None) -> dict:
                                       else None), ignore_slot=td.ignore_feature_group,
                         hadoop_home=td.hdfs.home if td.has("hdfs") else "",
                         nthreads=flags.num_threads, parser=getattr(flags, "parser", "cpu"),
-                        device=device)
+                        device=device, split=getattr(flags, "slot_split", "host"),
+                        resident=str(getattr(device, "type", device)).startswith("cuda"))
     data = reader.read()
     cfg = DarlinConfig.from_lm(lm, seed=flags.seed)
     t0 = time.time()
@@ -397,7 +407,10 @@ def run_darlin(lm, comm, device, flags, printer=None) -> dict:
                                               else None)
     prog = tr.train(printer=pr)
     out = {"examples": tr.num_ex, "passes": len(prog), "seconds": time.time() - t0,
-           "progress": prog[-1] if prog else None, "trainer": tr}
+           "progress": prog[-1] if prog else None, "trainer": tr,
+           "parser": reader.parser, "slot_split": reader.split,
+           "deferred_chunks": reader.deferred_chunks,
+           "split_deferred_chunks": reader.split_deferred_chunks}
     mo = lm.model_output
     if lm.has("model_output") and mo.has("file") and mo.format == "TEXT":
         d = os.path.dirname(mo.file[0])

@@ -3,7 +3,7 @@
 // dense unit -- Darlin BCD (bcd.hip), the bf16 GEMMs (gemm.hip, gemm256.hip), embeddings /
 // wide & deep / Adam (embedding.hip) and spmv (spmv.hip). The other kernel families are
 // bound in bind_launch.cpp, bind_table.cpp, bind_tploc.cpp, bind_prep.cpp, bind_linear.cpp,
-// bind_scoretext.cpp.
+// bind_scoretext.cpp, bind_slotsplit.cpp.
 #include <cmath>
 
 #include "bcd.h"
@@ -664,4 +664,5 @@ PYBIND11_MODULE(_hipops, m) {
   register_linear(m);
   register_dense(m);
   register_scoretext(m);
+  register_slotsplit(m);
 }

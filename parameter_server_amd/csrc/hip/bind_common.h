@@ -33,6 +33,7 @@ void register_prep(py::module_& m);      // localisation, sort / scan / RLE, fil
 void register_linear(py::module_& m);    // linear / predict / FM, the generator
 void register_dense(py::module_& m);     // Darlin BCD, GEMMs, embedding, spmv
 void register_scoretext(py::module_& m); // prediction lines
+void register_slotsplit(py::module_& m); // split by feature group
 
 inline hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
