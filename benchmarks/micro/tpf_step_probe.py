@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What bounds the flat step kernel (csrc/hip/tploc.hip tpf_step)? Times, on
+"""What bounds the flat step kernel (csrc/hip/tploc_step.hip tpf_step)? Times, on
 one localised 65,536 x 39 Criteo-shaped minibatch after a few training steps: the pull
 half, the update half, both in one launch, an empty launch (all counts 0), and the
 compact path's kv_resolve of the same distinct keys, for table capacities 2^22 / 2^26 /

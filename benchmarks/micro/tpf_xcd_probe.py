@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Device-only times of the flat bucket-geometry kernels (csrc/hip/tploc.hip) on one
+"""Device-only times of the flat bucket-geometry kernels (csrc/hip/tploc_bucket.hip, tploc_step.hip) on one
 localised 65,536 x 39 Criteo-shaped minibatch after a few training steps, for comparing two
 trees (e.g. block -> bucket-group maps: tpf_xcd_group_of): the bucket kernel alone
 (localize_tpf stage 2), the tpf_step pull / update / both, and the 8-owner exchange's

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-phase shader-clock durations of the tp bucket kernel (tploc.hip TP_MARK):
+"""Per-phase shader-clock durations of the tp bucket kernel (tploc_bucket.hip, prof marks):
 average over workgroups of (mark k - mark k-1), one 65,536 x 39 Criteo minibatch; then
 the fused forward + backward kernel (FB_MARK) on the compact and on the flat layout."""
 import os
@@ -34,7 +34,7 @@ t0 = rt0.min()
 print(f"  wall (realtime, us): last start {(rt0.max() - t0) / 100:.1f}, "
       f"last end {(rt1.max() - t0) / 100:.1f}, mean duration {((rt1 - rt0) / 100).mean():.1f}")
 
-# ---- fused forward + backward (tploc.hip tp_fwd_bwd FB_MARK) ----
+# ---- fused forward + backward (tploc_fused.hip tp_fwd_bwd FB_MARK) ----
 from parameter_server_amd.ops.linear import AUC_BINS, linear_fwd_bwd, new_accum  # noqa: E402
 from parameter_server_amd.ops.native import hipops  # noqa: E402
 

@@ -1,5 +1,6 @@
-// Bindings of tploc.hip: the tile / flat localiser, the fused forward / backward and the
-// fused step.
+// Bindings of the tp / tpf kernel family (launchers: tploc.h): the tile localiser
+// (tploc.hip, tploc_bucket.hip), the flat one (tploc_flat.hip), the fused forward / backward
+// (tploc_fused.hip) and the fused step and flat exchange (tploc_step.hip).
 #include "bind_common.h"
 #include "countmin.cuh"
 #include "tploc.h"
@@ -181,7 +182,7 @@ void check_tpf(const TpfBufs& f, int64_t n, int bits, const char* what, bool par
   need(f.slot_u, at::kInt, "slot_u", g * psamd::tpf_key_region());
 }
 
-// filt (the fused tail filter, tploc.hip tpf_filter_unit): (cells int32 [the sketch's
+// filt (the fused tail filter, tploc_flat.hip tpf_filter_unit): (cells int32 [the sketch's
 // byte cells as words], rsize, rshift, k, vmax, freq, ecnt uint8 [>= tpf_stride_max(n)],
 // w_ent float32 [the FlatLoc's tile-entry weights][, cnt_pre int32 [like cnt]: the
 // unfiltered counts])
@@ -326,7 +327,7 @@ Launch make_tpf_step(int64_t n, int bits, optional<py::tuple> A_, optional<Tenso
 }  // namespace
 
 void psamd_bind::register_tploc(py::module_& m) {
-  // ---------------- tile dedup + bucket partition localisation (tploc.hip) ----------------
+  // ------ tile dedup + bucket partition localisation (tploc.hip; fused: tploc_fused.hip) ------
   m.def("tploc_stride", [](int64_t n) { return psamd::tploc_stride(n); });
   // flat layout: entry stride of n keys / bound over minibatches of <= n keys / log2 tile
   m.def("tpf_stride", [](int64_t n) { return psamd::tpf_stride(n); });
@@ -407,11 +408,11 @@ void psamd_bind::register_tploc(py::module_& m) {
                      cur_stream());
   });
   m.def("tp_fwd_bwd_supported", [](int width) { return psamd::tp_fwd_bwd_supported(width); });
-  // ---- flat 1-GPU layout (tploc.hip "tpf")
+  // ---- flat 1-GPU layout ("tpf": tploc_bucket.hip, tploc_flat.hip, tploc_step.hip)
   m.def("tpf_groups", [](int64_t n, int bits) { return psamd::tpf_groups(n, bits); });
   m.def("tpf_key_region", []() { return psamd::tpf_key_region(); });
   m.def("tpf_entry_region", []() { return psamd::tpf_entry_region(); });
-  // the logical bucket group of physical block bid (tploc.hip tpf_xcd_group_of), host side
+  // the logical bucket group of physical block bid (tploc.cuh tpf_xcd_group_of), host side
   m.def("tpf_xcd_group", [](int bid, int groups) {
     check(groups >= 1 && bid >= 0 && bid < groups, "tpf_xcd_group: 0 <= bid < groups");
     return psamd::tpf_xcd_group(bid, groups);

@@ -1,5 +1,5 @@
 // CountMin sketch cells shared by the filter kernels (filters.hip) and the flat
-// localiser's fused tail filter (tploc.hip).
+// localiser's fused tail filter (tploc_flat.hip).
 //
 // Reference CountMin<K, uint8> (src/util/countmin.h:8-48): k probes by double hashing of
 // the 64->32 sketch hash (src/util/sketch.h:20-33), saturating uint8 counters (v_max 254,

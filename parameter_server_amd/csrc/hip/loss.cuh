@@ -1,5 +1,5 @@
 // Per-example loss terms shared by the linear-model forward kernels (linear.hip,
-// tploc.hip). Reference: LogitLoss / SquareHingeLoss ... (src/app/linear_method/loss.h:75-97).
+// tploc_fused.hip). Reference: LogitLoss / SquareHingeLoss ... (src/app/linear_method/loss.h:75-97).
 #pragma once
 #include "common.cuh"
 

@@ -1,5 +1,7 @@
-// Host entry points of tploc.hip: tile dedup + bucket partition localisation ("tp"),
-// its flat 1-GPU layout ("tpf"), the fused forward / backward and the fused step.
+// Host entry points of tploc.hip / tploc_bucket.hip / tploc_flat.hip / tploc_fused.hip /
+// tploc_step.hip: tile dedup + bucket partition localisation ("tp"), its flat 1-GPU layout
+// ("tpf"), the fused forward / backward and the fused step (device helpers: tploc.cuh,
+// host: tploc_geom.h).
 // n: keys of the minibatch; bits: key bits (KeyMix); *_cap: capacity of the buffer
 // before it. Entry buffers hold >= tploc_stride(n) (tp) / tpf_stride(n) (tpf) elements.
 #pragma once

@@ -150,7 +150,7 @@ def linear_fwd_bwd(loc, w_local, labels, *, B: int, width: int = 0, row_ptr=None
                    vals=None, loss="logit", coef=None, metrics=None, hist=None, update=None):
     """Forward (loss, dL/dm, metrics, AUC histogram) and backward into loc.grad of one
     minibatch; returns (coef, grad). A fixed-width "tp" localisation runs ONE fused
-    per-tile kernel plus the entry scan (tploc.hip tp_fwd_bwd: no per-occurrence
+    per-tile kernel plus the entry scan (tploc_fused.hip tp_fwd_bwd: no per-occurrence
     local-column gather, no coef round trip through memory); anything else runs
     linear_forward + linear_backward.
 

@@ -24,7 +24,7 @@ import torch
 from .keymix import mix, to_unsigned_order
 from .native import hipops, is_gpu
 
-TP_TILE = 8192  # occurrences per tp tile (csrc/hip/tploc.hip tp::kTile)
+TP_TILE = 8192  # occurrences per tp tile (csrc/hip/tploc.cuh tp::kTile)
 
 
 @dataclass
@@ -60,7 +60,7 @@ class TileInfo:
 @dataclass
 class FlatLoc:
     """A minibatch localised into the flat per-bucket layout (``Localizer(mode="tpf")``,
-    csrc/hip/tploc.hip "tpf"; the 1-GPU fused step). Bucket workgroup b owns fixed
+    csrc/hip/tploc_flat.hip; the 1-GPU fused step, tploc_step.hip). Bucket workgroup b owns fixed
     regions: keys ``uniqf[b * key_region + unit * key_region / 2 + j]``, entries
     ``ent_pos`` (tile entry id) / ``ent_j`` (key index) at ``b * entry_region``, live
     counts ``cnt[b] = (D0, E0, D1, E1)``; ``slot_u`` receives each key's table slot at
@@ -127,7 +127,7 @@ class Localizer:
     positions inside a key's segment (5 launches instead of 16).
     ``check()`` raises if a bucket overflowed its LDS hash (never for mixed keys of
     realistic batches; the bucket count bounds the distinct keys per bucket).
-    ``mode="tp"`` (csrc/hip/tploc.hip, GPU, key bits <= 34, <= 5.2 M keys): LDS dedup of
+    ``mode="tp"`` (csrc/hip/tploc.hip + tploc_bucket.hip, GPU, key bits <= 34, <= 5.2 M keys): LDS dedup of
     TP_TILE (8192)-occurrence tiles, then one workgroup per key-range bucket deduplicates the
     tile-distinct entries (a hot key is at most one entry per tile) and emits sorted
     unique keys, an entry-level CSC and local columns: 4 launches, no global atomics;
@@ -146,7 +146,7 @@ class Localizer:
                  tail_filter=None):
         self.max_nnz = int(max_nnz)
         # "tpf": (CountMinSketch with key_bits = bits, freq) -> the fused tail filter of the
-        # bucket kernel (tploc.hip tpf_filter_unit): filtered keys leave the minibatch
+        # bucket kernel (tploc_flat.hip tpf_filter_unit): filtered keys leave the minibatch
         self.tail_filter = tail_filter
         # "tpf": rank-sort each bucket's keys (the multi-GPU exchange rows stay key-ordered)
         self.sorted_keys = bool(sorted_keys)
@@ -191,7 +191,7 @@ class Localizer:
             H = hipops()
             N = H.tploc_stride(n)
             i32 = lambda k: torch.empty(k, dtype=torch.int32, device=dev)  # noqa: E731
-            # zeroed once: the bucket look-back's status words + launch epoch (tploc.hip)
+            # zeroed once: the bucket look-back's status words + launch epoch (tploc_bucket.hip)
             self.ptemp = torch.zeros(H.tploc_temp_bytes(n, self.bits), dtype=torch.uint8,
                                      device=dev)
             self.t_dcnt, self.t_rep = i32(N // TP_TILE), torch.empty(n, dtype=torch.int16, device=dev)

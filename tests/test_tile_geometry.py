@@ -1,5 +1,5 @@
 """Host-side geometry of the flat localisation (tploc.hip tp_flat_lts / tpf_stride /
-tpf_stride_max): tiles of 1024..8192 occurrences chosen from the minibatch size, and the
+tpf_stride_max, the host side of that unit): tiles of 1024..8192 occurrences chosen from the minibatch size, and the
 workspace bound that lets a Localizer sized for n keys take any smaller minibatch. Pure
 host functions of the built extension: run on CPU (skipped when it is not built)."""
 import pytest

@@ -1,4 +1,4 @@
-"""Fused per-tile forward + backward on a "tp" localisation (tploc.hip tp_fwd_bwd)
+"""Fused per-tile forward + backward on a "tp" localisation (tploc_fused.hip tp_fwd_bwd)
 against the plain PyTorch fp32 reference of the same step (margins, dL/dm, loss /
 accuracy / AUC histogram, gradient per unique key)."""
 import pytest

@@ -1,4 +1,4 @@
-"""The fused forward + backward kernel (tploc.hip tp_fwd_bwd_kernel) evaluates each
+"""The fused forward + backward kernel (tploc_fused.hip tp_fwd_bwd_kernel) evaluates each
 row's loss terms in ONE thread (margins and coefs go through LDS row arrays) instead of
 in all eight lanes of the row's group: every register-pass instantiation and both
 layouts (compact "tp", flat "tpf") against the plain PyTorch fp32 reference of

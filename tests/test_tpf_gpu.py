@@ -1,4 +1,5 @@
-"""Flat 1-GPU layout (Localizer mode "tpf", csrc/hip/tploc.hip tpf_*): the localisation
+"""Flat 1-GPU layout (Localizer mode "tpf", csrc/hip/tploc_bucket.hip, tploc_flat.hip and
+tploc_step.hip): the localisation
 covers every occurrence exactly, and the fused 1-GPU step built on it (pull issued in the
 previous step's update launch, fused forward + tile backward, per-bucket fixed-point
 gradient sums + optimizer update) trains the table a plain-PyTorch fp32 FTRL / AdaGrad /

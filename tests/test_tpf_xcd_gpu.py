@@ -1,5 +1,5 @@
-"""The block -> bucket-group map of the flat bucket-geometry kernels (csrc/hip/tploc.hip
-tpf_xcd_group_of: the blocks of one XCD take a contiguous range of groups). The map is a
+"""The block -> bucket-group map of the flat bucket-geometry kernels (csrc/hip/tploc.cuh
+tpf_xcd_group_of, used by the kernels of tploc_step.hip: the blocks of one XCD take a contiguous range of groups). The map is a
 permutation of the groups, and the kernels that use it (tpf_step, tpf_unpack_w,
 tpf_pack_grads) still compute what they did next to the ones that take their group from
 blockIdx.x (tpf_bucket, tpf_filter, tpf_pack_keys; every region is indexed by the logical

@@ -1,7 +1,8 @@
-"""Tile dedup + bucket partition localisation (csrc/hip/tploc.hip, mode "tp") against
+"""Tile dedup + bucket partition localisation (csrc/hip/tploc.hip + tploc_bucket.hip, mode "tp") against
 the plain-PyTorch localisation: identical sorted unique keys and local columns; the
 entry-level CSC groups every tile-distinct entry under its key; the backward
-(per-tile LDS accumulation + segmented scan over entries) matches an fp64 reference."""
+(csrc/hip/tploc_fused.hip: per-tile LDS accumulation + segmented scan over entries)
+matches an fp64 reference."""
 import pytest
 import torch
 
