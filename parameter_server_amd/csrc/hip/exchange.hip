@@ -186,7 +186,10 @@ void xchg_unpack_w(const float* recv_w, const int32_t* perm, const int32_t* n_un
 // ceil(C * nb / 4) words of nb-byte fixed-point codes; header words [2], [3] hold
 // the row's min / max as order-preserving ints (max gets +1e-6 when decoded, as
 // the reference does). Stochastic rounding draws from a counter RNG keyed by
-// (seed, device step clock, row, index), so graph replays draw fresh bits.
+// (seed, device step clock, row, index), so graph replays draw fresh bits. A NaN filter
+// mark does not survive the codes: it stays out of the row's min / max and leaves every
+// other entry's code alone, but decodes to some value of the row's range (the trainers
+// never send one through FixingFloat).
 __device__ __forceinline__ int ff_ord(float f) {
   const int b = __float_as_int(f);
   return b >= 0 ? b : b ^ 0x7fffffff;
