@@ -9,7 +9,9 @@ the same minibatches already in HBM.
 kind = criteo: 39 binary features per row (power-law ids, "k:1" LIBSVM, zero-padded ids),
        rcv1:   5..145 features per row (~75), tf-idf-like values,
        ctr:    the criteo rows in the slot-grouped SPARSE_BINARY text of the reference's CTR
-               confs, one key per group: "1; 01 00001234; 02 00420000; ...; 39 00000007"."""
+               confs, one key per group: "1; 01 00001234; 02 00420000; ...; 39 00000007",
+       adfea:  the criteo rows as ADFEA log lines, one key per group:
+               "00000017 1 1 00001234:01 00420000:02 ... 00000007:39"."""
 from __future__ import annotations
 
 import argparse
@@ -72,6 +74,37 @@ def _write_ctr_fast(path, keys, y, N):
     out.tofile(path)
 
 
+def _write_adfea_fast(path, keys, y, N):
+    """The same rows as ADFEA text (the grammar of data.synthetic.write_text: "lineid 1 click
+    key:grp ..."), one key per group, groups 01..39, built like _write_criteo_fast
+    (zero-padded ids parse as the same integers)."""
+    per, width = keys.shape
+    nd = len(str(N - 1))
+    tok = nd + 4  # " " digits ":gg"
+    head = 8 + 4  # line id, " 1 ", click
+    out = np.empty((per, head + width * tok + 1), dtype=np.uint8)
+    i = np.arange(per)
+    for p in range(7, -1, -1):
+        out[:, p] = ord("0") + (i % 10)
+        i //= 10
+    out[:, 8] = ord(" ")
+    out[:, 9] = ord("1")
+    out[:, 10] = ord(" ")
+    out[:, 11] = np.where(y > 0, ord("1"), ord("0"))
+    body = out[:, head:-1].reshape(per, width, tok)
+    body[:, :, 0] = ord(" ")
+    k = keys.copy()
+    for p in range(nd - 1, -1, -1):
+        body[:, :, 1 + p] = ord("0") + (k % 10)
+        k //= 10
+    g = np.arange(1, width + 1)
+    body[:, :, 1 + nd] = ord(":")
+    body[:, :, 2 + nd] = ord("0") + g // 10
+    body[:, :, 3 + nd] = ord("0") + g % 10
+    out[:, -1] = ord("\n")
+    out.tofile(path)
+
+
 def _breakdown(tr, d, a, steps, cache):
     """Where a cached run's time goes: the feeder alone (pread -> pinned -> HBM, no
     training) and the trainer alone (the same step count on one HBM-resident minibatch)."""
@@ -97,7 +130,7 @@ def _breakdown(tr, d, a, steps, cache):
     feed_s = time.time() - t0
     out = {"source": "breakdown", "feeder_only_examples_per_s": ex / feed_s,
            "feeder_only_h2d_gb_per_s": f.bytes_h2d / feed_s / 1e9, "feeder_batches": n}
-    if last is not None and a.kind in ("criteo", "ctr"):
+    if last is not None and a.kind in ("criteo", "ctr", "adfea"):
         keys, labels = last
         for _ in range(3):
             tr.step(keys, labels, width=39)
@@ -112,7 +145,7 @@ def _breakdown(tr, d, a, steps, cache):
 
 
 def _text_format(kind):
-    return "SPARSE_BINARY" if kind == "ctr" else "LIBSVM"
+    return {"ctr": "SPARSE_BINARY", "adfea": "ADFEA"}.get(kind, "LIBSVM")
 
 
 def write_files(d, kind, rows, files, seed=0, N=10 ** 8):
@@ -120,10 +153,11 @@ def write_files(d, kind, rows, files, seed=0, N=10 ** 8):
     per = rows // files
     for f in range(files):
         print(f"[bench_app] writing file {f + 1} / {files}", file=sys.stderr, flush=True)
-        if kind in ("criteo", "ctr"):
+        if kind in ("criteo", "ctr", "adfea"):
             keys = np.sort((N * rng.random((per, 39)) ** 4).astype(np.int64), axis=1)
             y = np.where(rng.random(per) < 0.3, 1, -1)
-            write = _write_criteo_fast if kind == "criteo" else _write_ctr_fast
+            write = {"criteo": _write_criteo_fast, "ctr": _write_ctr_fast,
+                     "adfea": _write_adfea_fast}[kind]
             write(os.path.join(d, f"part-{f:03d}"), keys, y, N)
             continue
         if kind == "criteo_slow":
@@ -154,7 +188,7 @@ def main():
     ap.add_argument("--rows", type=int, default=2_000_000)
     ap.add_argument("--files", type=int, default=8)
     ap.add_argument("--minibatch", type=int, default=10000)
-    ap.add_argument("--kind", default="criteo", choices=["criteo", "criteo_slow", "rcv1", "ctr"])
+    ap.add_argument("--kind", default="criteo", choices=["criteo", "criteo_slow", "rcv1", "ctr", "adfea"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--dir", default="")
     ap.add_argument("--cache", type=int, default=1,

@@ -7,6 +7,10 @@ alternating in one process on the same files, no cache. Prints one JSON line.
         --parser cpu,gpu,gpu,gpu,cpu,gpu,gpu,gpu \\
         --split host,host,device,resident,host,host,device,resident
 
+``--format ADFEA`` / ``TERAFEA`` reads CTR-log text instead (adtext.hip on the device
+routes): ``data.synthetic.sparse_groups``-shaped rows, ``--present`` of ``--groups`` feature
+groups per row with one key each, written by a fast fixed-width writer.
+
 ``--split`` pairs with ``--parser`` entry by entry (a shorter list repeats its last entry):
 ``host``, ``device``, or ``resident`` (``device`` with ``resident=True``). ``--warmup N``
 reads every distinct route N times first, untimed. ``--csc`` also builds a ``DarlinTrainer``
@@ -21,12 +25,59 @@ import sys
 import tempfile
 import time
 
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
+def _digits(out, v, nd):
+    """``v`` as ``nd`` zero-padded decimal digits into the last axis of ``out``."""
+    v = v.copy()
+    for p in range(nd - 1, -1, -1):
+        out[..., p] = ord("0") + (v % 10).astype(np.uint8)
+        v //= 10
+
+
+def write_group_files(d, fmt, rows, files, groups, present, seed=0, N=10 ** 6):
+    """``sparse_groups``-shaped rows as ADFEA ("lineid 1 click key:grp ...") or TERAFEA
+    ("click lineid | key ...", key = grp << 54 | id) text: ``present`` of ``groups`` groups per
+    row in ascending order, one key each, fixed-width tokens built by digit arithmetic."""
+    rng = np.random.default_rng(seed)
+    per = rows // files
+    for f in range(files):
+        g = np.sort(np.argsort(rng.random((per, groups)), axis=1)[:, :present] + 1, axis=1)
+        k = (N * rng.random((per, present)) ** 3).astype(np.uint64)
+        y = rng.random(per) < 0.3
+        i = np.arange(per, dtype=np.uint64)
+        if fmt == "ADFEA":
+            tok, head = 1 + 7 + 1 + 4, 8 + 4  # " kkkkkkk:gggg"; "iiiiiiii 1 c"
+            out = np.full((per, head + present * tok + 1), ord(" "), dtype=np.uint8)
+            _digits(out[:, :8], i, 8)
+            out[:, 9] = ord("1")
+            out[:, 11] = np.where(y, ord("1"), ord("0"))
+            body = out[:, head:-1].reshape(per, present, tok)
+            _digits(body[:, :, 1:8], k, 7)
+            body[:, :, 8] = ord(":")
+            _digits(body[:, :, 9:13], g.astype(np.uint64), 4)
+        else:
+            tok, head = 1 + 20, 1 + 1 + 8 + 2  # " " 20 digits; "c iiiiiiii |"
+            out = np.full((per, head + present * tok + 1), ord(" "), dtype=np.uint8)
+            out[:, 0] = np.where(y, ord("1"), ord("0"))
+            _digits(out[:, 2:10], i, 8)
+            out[:, 11] = ord("|")
+            body = out[:, head:-1].reshape(per, present, tok)
+            _digits(body[:, :, 1:21], (g.astype(np.uint64) << np.uint64(54)) | k, 20)
+        out[:, -1] = ord("\n")
+        out.tofile(os.path.join(d, f"part-{f:03d}"))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--format", default="SPARSE_BINARY",
+                    choices=["SPARSE_BINARY", "ADFEA", "TERAFEA"])
+    ap.add_argument("--groups", type=int, default=100)
+    ap.add_argument("--present", type=int, default=20)
     ap.add_argument("--rows", type=int, default=2_000_000)
     ap.add_argument("--files", type=int, default=8)
     ap.add_argument("--threads", type=int, default=16)
@@ -43,7 +94,11 @@ def main():
     from parameter_server_amd.data.slot_reader import SlotData, SlotReader
 
     d = a.dir or tempfile.mkdtemp(prefix="psamd_slots_")
-    write_files(d, "ctr", a.rows, a.files)
+    fmt = a.format
+    if fmt == "SPARSE_BINARY":
+        write_files(d, "ctr", a.rows, a.files)
+    else:
+        write_group_files(d, fmt, a.rows, a.files, a.groups, a.present)
     files = sorted(os.path.join(d, f) for f in os.listdir(d) if f.startswith("part-"))
     mb = sum(os.path.getsize(f) for f in files) / 1e6
     parsers = a.parser.split(",")
@@ -52,7 +107,7 @@ def main():
     routes = list(zip(parsers, splits))
 
     def reader(parser, split):
-        return SlotReader(files, "SPARSE_BINARY", nthreads=a.threads, parser=parser, device="cuda",
+        return SlotReader(files, fmt, nthreads=a.threads, parser=parser, device="cuda",
                           split="host" if split == "host" else "device",
                           resident=split == "resident")
 
@@ -80,9 +135,9 @@ def main():
     # where the time goes: the parse alone of one file on either route, and the split by slot
     raw = open(files[0], "rb").read()
     t0 = time.time()
-    b = data.parse_text(raw, "SPARSE_BINARY", ignore_slot=False, nthreads=a.threads)
+    b = data.parse_text(raw, fmt, ignore_slot=False, nthreads=a.threads)
     t_host = time.time() - t0
-    r = SlotReader(files[:1], "SPARSE_BINARY", parser="gpu", device="cuda")
+    r = SlotReader(files[:1], fmt, parser="gpu", device="cuda")
     r._parse_device(files[0])
     torch.cuda.synchronize()
     t0 = time.time()
@@ -94,8 +149,8 @@ def main():
     one = {"rows": b.rows, "host_parse_s": round(t_host, 3),
            "device_parse_and_copy_back_s": round(t_dev, 3), "split_by_slot_s": round(t_split, 3)}
     if any(s != "host" for s in splits):
-        one.update(_device_split_times(files[0]))
-    out = {"bench": "slot_reader", "files": a.files, "text_mb": round(mb, 1),
+        one.update(_device_split_times(files[0], fmt))
+    out = {"bench": "slot_reader", "format": fmt, "files": a.files, "text_mb": round(mb, 1),
            "threads": a.threads, "runs": runs, "one_file": one}
     print(json.dumps(out), flush=True)
     if a.csc:  # (a line of its own: the trainers take longer than everything above)
@@ -103,20 +158,21 @@ def main():
                           "prep_times": _csc_times(read)}), flush=True)
 
 
-def _device_split_times(path: str) -> dict:
+def _device_split_times(path: str, fmt: str) -> dict:
     """One file on the device: the parse alone (nothing copied back), the split of the parsed
     chunks alone, and the whole resident read of the file."""
     import torch
 
-    from parameter_server_amd.data.slot_reader import SlotReader
-    from parameter_server_amd.ops.pstext import parse_ps_text_device
+    from parameter_server_amd.data.slot_reader import SlotReader, _device_parser
     from parameter_server_amd.ops.slotsplit import split_by_slot
+
+    parse_device = _device_parser(fmt)
 
     def parse():
         with open(path, "rb") as f:
             chunks = SlotReader._text_chunks(f.read())
-        return [parse_ps_text_device(torch.frombuffer(bytearray(c), dtype=torch.uint8).to("cuda"),
-                                     "SPARSE_BINARY", ignore_slot=False, host=c) for c in chunks]
+        return [parse_device(torch.frombuffer(bytearray(c), dtype=torch.uint8).to("cuda"), fmt,
+                             ignore_slot=False, host=c) for c in chunks]
 
     def split(parsed):
         return [split_by_slot(None, p.row_ptr, p.keys, p.vals, p.slots) for p in parsed]
@@ -130,7 +186,7 @@ def _device_split_times(path: str) -> dict:
     sp = split(parsed)
     torch.cuda.synchronize()
     t2 = time.time()
-    r = SlotReader([path], "SPARSE_BINARY", parser="gpu", split="device", resident=True,
+    r = SlotReader([path], fmt, parser="gpu", split="device", resident=True,
                    device="cuda")
     r.read()
     torch.cuda.synchronize()

@@ -199,7 +199,8 @@ bool parse_adfea(const char* p, const char* e, const ParseOptions& opt, LineSink
   // lineid 1 click key:grp key:grp ...
   const char *tb, *te;
   uint64_t key = 0;
-  for (int i = 0; next_tok(p, e, " :\t\r", tb, te); ++i) {
+  int i = 0;
+  for (; next_tok(p, e, " :\t\r", tb, te); ++i) {
     if (i < 2) continue;
     if (i == 2) {
       int64_t c;
@@ -213,7 +214,7 @@ bool parse_adfea(const char* p, const char* e, const ParseOptions& opt, LineSink
       s.add((int)g, key, 1.f, false);
     }
   }
-  return true;
+  return i >= 3;  // (a line that ends before its label is no example: a bad line)
 }
 
 bool parse_terafea(const char* p, const char* e, const ParseOptions& opt, LineSink& s) {

@@ -26,7 +26,8 @@ device slots; ``release(batch)`` after the step that reads it was issued):
 
 The text source has two parsers (``parser=``). ``"cpu"`` (the default) is the path above.
 ``"gpu"`` parses LIBSVM / CRITEO text (ops/textparse.py, textparse.hip) and the slot-grouped
-SPARSE_BINARY / SPARSE text of the CTR confs (ops/pstext.py, pstext.hip) on the device:
+SPARSE_BINARY / SPARSE text of the CTR confs (ops/pstext.py, pstext.hip) and ADFEA text
+(ops/adtext.py, adtext.hip) on the device:
 reader threads read each file straight into pinned chunk buffers of ``chunk_bytes``, cut at
 the last newline; a chunk is copied to HBM on the copy stream and parsed on a parse stream
 into one of a ring of device output buffers; minibatches are slices of the parsed chunk
@@ -34,8 +35,9 @@ into one of a ring of device output buffers; minibatches are slices of the parse
 that span files: rows left over are carried to the front of the next chunk's output by a
 device-to-device copy). A chunk the kernels decline (a malformed or ``#`` line, a number
 outside their exact domain, a line longer than a chunk) is parsed by the CPU parser from
-the pinned copy of the same bytes (``deferred_chunks``). Other formats,
-``max_lines_per_file > 0`` and ``device="cpu"`` use the CPU parser whatever ``parser``
+the pinned copy of the same bytes (``deferred_chunks``). TERAFEA has a device parser
+(ops/adtext.py, used by ``SlotReader``) but stays on the CPU parser here for now. Other
+formats, ``max_lines_per_file > 0`` and ``device="cpu"`` use the CPU parser whatever ``parser``
 says; ``"auto"`` picks the GPU parser where it applies.
 
 With ``device="cpu"`` the same interface yields CPU tensors (no pinned memory, no
@@ -54,7 +56,7 @@ import torch
 
 from . import TEXT_FORMATS, ExampleBatch, StreamReader, read_file
 from . import bincache
-from ..ops import pstext, textparse
+from ..ops import adtext, pstext, textparse
 
 
 @dataclass
@@ -166,7 +168,9 @@ class DeviceFeeder:
         self.parser = "gpu" if (parser != "cpu" and self.gpu and max_lines_per_file <= 0
                                 and (textparse.supported(self._fmt_id)
                                      # (group heads are validated only when slots are kept)
-                                     or (pstext.supported(self._fmt_id) and ignore_slot))
+                                     or (pstext.supported(self._fmt_id) and ignore_slot)
+                                     # (TERAFEA keeps the CPU parser in the feeder)
+                                     or (self._fmt_id == TEXT_FORMATS["ADFEA"] and ignore_slot))
                                 ) else "cpu"
         self.chunk_bytes = max(1024, int(chunk_bytes))
         self.text_chunks = 0      # chunks of text handed to the device parser
@@ -475,6 +479,7 @@ class DeviceFeeder:
             # (the formats whose chunks keep a value per feature; the others are binary)
             valued = self._fmt_id in (TEXT_FORMATS["LIBSVM"], TEXT_FORMATS["SPARSE"])
             grouped = pstext.supported(self._fmt_id)
+            adlog = adtext.supported(self._fmt_id)
             carry = None     # rows parsed but not yet cut into a minibatch
             pieces = []      # host copies of the current file's arrays (cache_dir)
             nxt = fetch()
@@ -507,8 +512,10 @@ class DeviceFeeder:
                     if cur[0] == "chunk":
                         _, i, n, f, d, ev = cur
                         ps.wait_event(ev)
-                        if grouped:  # (minibatches carry no slot ids: the group heads are not read)
-                            res = pstext.parse_ps_text_device(
+                        if grouped or adlog:  # (minibatches carry no slot ids: groups are not read)
+                            parse = adtext.parse_ad_text_device if adlog else \
+                                pstext.parse_ps_text_device
+                            res = parse(
                                 d, self._fmt_id, self.num_features, ignore_slot=True, out=st,
                                 row0=r0, nnz0=n0, n=n, host=tp["pin"][i])
                         else:

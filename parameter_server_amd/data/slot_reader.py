@@ -12,9 +12,9 @@ Here files are parsed by the C++ runtime (``_pscore.parse_text``), the cache is
 slot info follows the reference ``InfoParser`` (src/data/info_parser.cc:10-48):
 ``max_key`` is exclusive (max + 1), label slot 0 has range [0, 1).
 
-``parser="gpu"`` with a GPU ``device`` parses SPARSE_BINARY / SPARSE files on the device on
-a cache miss (ops/pstext.py: <= 32 MiB chunks cut at a newline, slot ids included); the
-arrays come back as an ``ExampleBatch`` and go through the same split and cache. Other
+``parser="gpu"`` with a GPU ``device`` parses SPARSE_BINARY / SPARSE files (ops/pstext.py)
+and ADFEA / TERAFEA files (ops/adtext.py) on the device on a cache miss (<= 32 MiB chunks
+cut at a newline, slot ids included); the arrays come back as an ``ExampleBatch`` and go through the same split and cache. Other
 formats, ``.gz`` / ``hdfs://`` paths and CPU devices stay on the host parser, and so does
 ``parser="auto"``: with the split by slot on the host, which then bounds the load, the device
 parser measured no faster than the host route.
@@ -29,7 +29,8 @@ from a copy when resident); a cache hit returns numpy arrays on every route. Mea
 (benchmarks/bench_slotreader.py, 2 M rows in 8 files): 0.72-0.76 s, resident 0.62-0.65 s,
 against 0.90-0.96 s on the host route; it is opt-in all the same, the defaults and ``"auto"``
 are unchanged. ``split_deferred_chunks`` counts the chunks ``SlotData.from_batch`` took after
-all (more than 4096 slot ids, a row naming a group twice, too many cells).
+all (more than 4096 slot ids, a row naming a group twice, too many cells). TERAFEA does
+not promise that a row's groups are contiguous: such chunks take that way.
 """
 from __future__ import annotations
 
@@ -241,8 +242,9 @@ class SlotReader:
         are device tensors. None for a file without text (the host route's)."""
         import torch
 
-        from ..ops.pstext import parse_ps_text_device
         from ..ops.slotsplit import split_by_slot
+
+        parse = _device_parser(self.fmt)
 
         with open(path, "rb") as f:
             chunks = self._text_chunks(f.read())
@@ -251,7 +253,7 @@ class SlotReader:
         parts, nonunit = [], False
         for host in chunks:
             with torch.cuda.device(self.device):
-                res = parse_ps_text_device(
+                res = parse(
                     torch.frombuffer(bytearray(host), dtype=torch.uint8).to(self.device), self.fmt,
                     ignore_slot=self.ignore_slot, host=host)
                 self.deferred_chunks += bool(res.deferred)
@@ -280,14 +282,13 @@ class SlotReader:
         """One plain file through the device parser, chunk by chunk, as an ExampleBatch."""
         import torch
 
-        from ..ops.pstext import parse_ps_text_device
-
+        parse = _device_parser(self.fmt)
         with open(path, "rb") as f:
             raw = f.read()
         parts = []
         for host in self._text_chunks(raw):
             with torch.cuda.device(self.device):
-                res = parse_ps_text_device(
+                res = parse(
                     torch.frombuffer(bytearray(host), dtype=torch.uint8).to(self.device), self.fmt,
                     ignore_slot=self.ignore_slot, host=host)
                 self.deferred_chunks += bool(res.deferred)
@@ -377,9 +378,17 @@ def _is_gpu_device(device) -> bool:
 
 
 def _ps_supported(fmt) -> bool:
-    from ..ops.pstext import supported
+    """Whether a device parser that keeps slot ids knows ``fmt``."""
+    from ..ops import adtext, pstext
 
-    return supported(fmt)
+    return pstext.supported(fmt) or adtext.supported(fmt)
+
+
+def _device_parser(fmt):
+    """The device parser of ``fmt`` (ops/pstext.py and ops/adtext.py share one signature)."""
+    from ..ops import adtext, pstext
+
+    return adtext.parse_ad_text_device if adtext.supported(fmt) else pstext.parse_ps_text_device
 
 
 def _jsonable(info: dict) -> dict:

@@ -117,10 +117,23 @@ def criteo_slots(rows: int, *, seed: int = 0, row0: int = 0, num_features: int =
 
 def write_text(sd: SlotData, path: str, fmt: str = "SPARSE_BINARY"):
     """PS text format (reference text_parser.cc:200-250): ``label; g k[:v] k ...; ...``
-    or LIBSVM ``label k:v ...`` (groups merged)."""
+    or LIBSVM ``label k:v ...`` (groups merged). The CTR log formats, both binary (values
+    are dropped): ADFEA ``lineid 1 click key:grp ...`` and TERAFEA ``click lineid | key ...``
+    with the group in the key's top 10 bits, ``(g << 54) | (key & (2^54 - 1))``."""
     gids = sorted(sd.groups)
     with open(path, "w") as f:
         for i in range(sd.rows):
+            if fmt in ("ADFEA", "TERAFEA"):
+                click = 1 if sd.labels[i] > 0 else 0
+                toks = []
+                for g in gids:
+                    off, keys, _ = sd.groups[g]
+                    for k in keys[off[i]:off[i + 1]]:
+                        toks.append(f"{int(k)}:{g}" if fmt == "ADFEA" else
+                                    str((int(g) << 54) | (int(k) & ((1 << 54) - 1))))
+                head = [str(i), "1", str(click)] if fmt == "ADFEA" else [str(click), str(i), "|"]
+                f.write(" ".join(head + toks) + "\n")
+                continue
             y = 1 if sd.labels[i] > 0 else 0 if fmt != "LIBSVM" else -1
             parts = [str(y)]
             if fmt == "LIBSVM":

@@ -68,9 +68,12 @@ class TextParseBuffers:
     def cap_nnz(self) -> int:
         return self.keys.numel()
 
-    def reserve_work(self, n: int, ps: bool = False):
-        """Work space for ``n`` bytes of text (``ps``: for the parser of ops/pstext.py)."""
-        need = int(hipops().pstext_work_words(n) if ps else hipops().textparse_work_words(n))
+    def reserve_work(self, n: int, ps: bool = False, ad: bool = False):
+        """Work space for ``n`` bytes of text (``ps``: for the parser of ops/pstext.py,
+        ``ad``: for the one of ops/adtext.py)."""
+        words = hipops().adtext_work_words if ad else \
+            hipops().pstext_work_words if ps else hipops().textparse_work_words
+        need = int(words(n))
         if self.work is None or self.work.numel() < need:
             self.work = torch.empty(need, dtype=torch.int32, device=self.device)
 
