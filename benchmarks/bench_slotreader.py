@@ -163,16 +163,15 @@ def _device_split_times(path: str, fmt: str) -> dict:
     chunks alone, and the whole resident read of the file."""
     import torch
 
-    from parameter_server_amd.data.slot_reader import SlotReader, _device_parser
+    from parameter_server_amd.data.slot_reader import SlotReader
     from parameter_server_amd.ops.slotsplit import split_by_slot
-
-    parse_device = _device_parser(fmt)
+    from parameter_server_amd.ops.textparse import parse_text_device
 
     def parse():
         with open(path, "rb") as f:
             chunks = SlotReader._text_chunks(f.read())
-        return [parse_device(torch.frombuffer(bytearray(c), dtype=torch.uint8).to("cuda"), fmt,
-                             ignore_slot=False, host=c) for c in chunks]
+        return [parse_text_device(torch.frombuffer(bytearray(c), dtype=torch.uint8).to("cuda"),
+                                  fmt, ignore_slot=False, host=c) for c in chunks]
 
     def split(parsed):
         return [split_by_slot(None, p.row_ptr, p.keys, p.vals, p.slots) for p in parsed]

@@ -37,17 +37,11 @@
 // Safety on arbitrary bytes as in textparse.hip: reads clamped to n, sizes from the count
 // pass and checked before anything is emitted (sticky H_CAP), every emitted index guarded,
 // every token loop bounded by textnum::kMaxTok + 1.
-#include "adtext.h"
 #include "textparse.cuh"
-#include "../core/textnum.h"
-
-#include <stdexcept>
 
 namespace psamd {
 
 namespace {
-
-constexpr int kFmtAdfea = 4, kFmtTerafea = 6;  // data.TEXT_FORMATS
 
 // per-span summary (ad_count -> ad_scan) and per-span bases (ad_scan -> ad_emit)
 enum { S_FN, S_HEAD, S_NLAB, S_NENT, S_WORDS = 4 };
@@ -259,13 +253,9 @@ __global__ void __launch_bounds__(kTpBlk) ad_emit_kernel(
     const int i = __ffs((int)r) - 1;
     r &= r - 1;
     const int off = threadIdx.x * kTpBytes + i;
-    const int64_t g = base + off;
     const bool is_lab = (t.lab >> i) & 1u, is_key = (t.key >> i) & 1u, is_ent = (t.ent >> i) & 1u;
-    // the token's bytes: LDS when kMaxTok + 1 bytes from its start stay inside the span
-    // (bytes past n read as '\n' there), else global memory clamped to n
-    const int64_t left = n - g;
-    const int lim = (int)(left < textnum::kMaxTok + 1 ? left : textnum::kMaxTok + 1);
-    const uint8_t* p = off + textnum::kMaxTok + 1 <= kTpSpan ? lds_text + off : text + g;
+    int lim;
+    const uint8_t* p = tp_token_window(text, n, base, off, lds_text, &lim);
     int len = 0;
     for (; len < lim; ++len) {
       const uint32_t c = p[len];
@@ -299,58 +289,33 @@ __global__ void __launch_bounds__(kTpBlk) ad_emit_kernel(
     bad += st == textnum::kBad;
     defer += st == textnum::kDefer;
   }
-  // per-workgroup reduction; the header is touched only when there is something to add
-  const int nbad = __syncthreads_count(bad), ndef = __syncthreads_count(defer);
-  if (threadIdx.x == 0) {
-    if (nbad) atomicAdd(&hdr[H_BAD], nbad);
-    if (ndef) atomicAdd(&hdr[H_DEFER], ndef);
-  }
+  tp_report<false>(bad, defer, 0, hdr);
 }
 
 template <bool kAd>
-void ad_launch(const uint8_t* text, int64_t n, uint64_t hash_mod, int64_t row0, int64_t nnz0,
-               float* labels, int64_t cap_rows, int64_t* row_ptr, int64_t cap_rp, uint64_t* keys,
-               int32_t* slots, int64_t cap_nnz, int32_t* hdr, int32_t* work, hipStream_t st) {
+void ad_launch_as(const uint8_t* text, int64_t n, uint64_t hash_mod, const TextOut& o,
+                  int32_t* work, hipStream_t st) {
   const int64_t nb = (n + kTpSpan - 1) / kTpSpan;
   int32_t* sum = work;
   int32_t* bases = work + nb * S_WORDS;
-  const int fgrid = grid_for(n / 8 + 1, 256, 2048);
   ad_count_kernel<kAd><<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, sum);
-  ad_scan_kernel<kAd><<<1, kTpBlk, 0, st>>>(sum, bases, nb, row0, nnz0, cap_rows, cap_rp, cap_nnz,
-                                            row_ptr, hdr);
-  const auto emit = slots ? ad_emit_kernel<kAd, true> : ad_emit_kernel<kAd, false>;
-  emit<<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, bases, row0, nnz0, cap_rows, cap_nnz, labels,
-                                        row_ptr, keys, slots, hdr);
-  tp_finish_kernel<<<fgrid, 256, 0, st>>>(keys, row_ptr, row0, nnz0, false, hdr);
-  if (hash_mod) tp_mod_kernel<<<fgrid, 256, 0, st>>>(keys, nnz0, hash_mod, hdr);
-  PSAMD_HIP_CHECK(hipGetLastError());
+  ad_scan_kernel<kAd><<<1, kTpBlk, 0, st>>>(sum, bases, nb, o.row0, o.nnz0, o.cap_rows, o.cap_rp,
+                                            o.cap_nnz, o.row_ptr, o.hdr);
+  const auto emit = o.slots ? ad_emit_kernel<kAd, true> : ad_emit_kernel<kAd, false>;
+  emit<<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, bases, o.row0, o.nnz0, o.cap_rows, o.cap_nnz,
+                                        o.labels, o.row_ptr, o.keys, o.slots, o.hdr);
+  tp_finish(o, n, false, hash_mod, st);
 }
 
 }  // namespace
 
-int64_t adtext_work_words(int64_t n) {
-  return ((n + kTpSpan - 1) / kTpSpan) * (S_WORDS + B_WORDS);
-}
+int64_t ad_work_words(int64_t n) { return ((n + kTpSpan - 1) / kTpSpan) * (S_WORDS + B_WORDS); }
 
-// text: n bytes, 16-byte aligned. Outputs behind row0 rows / nnz0 features already in the
-// buffers. hdr: H_WORDS int32 (H_CAP must be cleared by the caller before the first use);
-// work: adtext_work_words(n) int32.
-void adtext(const uint8_t* text, int64_t n, int fmt, uint64_t hash_mod, int64_t row0,
-            int64_t nnz0, float* labels, int64_t cap_rows, int64_t* row_ptr, int64_t cap_rp,
-            uint64_t* keys, int32_t* slots, int64_t cap_nnz, int32_t* hdr, int32_t* work,
-            hipStream_t st) {
-  if (fmt != kFmtAdfea && fmt != kFmtTerafea)
-    throw std::invalid_argument("adtext: no device parser for this text format");
-  if (n <= 0 || n > ((int64_t)1 << 30))
-    throw std::invalid_argument("adtext: chunk size must be in [1, 2^30] bytes");
-  if (((uintptr_t)text & 15) != 0)
-    throw std::invalid_argument("adtext: text buffer must be 16-byte aligned");
-  if (fmt == kFmtAdfea)
-    ad_launch<true>(text, n, hash_mod, row0, nnz0, labels, cap_rows, row_ptr, cap_rp, keys, slots,
-                    cap_nnz, hdr, work, st);
-  else
-    ad_launch<false>(text, n, hash_mod, row0, nnz0, labels, cap_rows, row_ptr, cap_rp, keys,
-                     slots, cap_nnz, hdr, work, st);
+// Behind textparse()'s checks (textparse.hip). adfea: ADFEA, else TERAFEA.
+void ad_launch(const uint8_t* text, int64_t n, bool adfea, uint64_t hash_mod, const TextOut& o,
+               int32_t* work, hipStream_t st) {
+  if (adfea) ad_launch_as<true>(text, n, hash_mod, o, work, st);
+  else ad_launch_as<false>(text, n, hash_mod, o, work, st);
 }
 
 }  // namespace psamd

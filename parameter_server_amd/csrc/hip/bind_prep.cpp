@@ -1,14 +1,12 @@
 // Bindings of the data-preparation kernels: generic localisation (localize.hip,
 // primitives.hip, sort32.hip, partloc.hip), the filters (filters.hip) and the text
 // parsers / formatter (textparse.hip, pstext.hip, adtext.hip, modeltext.hip).
-#include "adtext.h"
 #include "bind_common.h"
 #include "filters.h"
 #include "localize.h"
 #include "modeltext.h"
 #include "partloc.h"
 #include "primitives.h"
-#include "pstext.h"
 #include "sort32.h"
 #include "textparse.h"
 
@@ -45,10 +43,12 @@ uint64_t cm_rsize(const Tensor& table, int64_t rsize, int rshift, int key_bits) 
 
 void psamd_bind::register_prep(py::module_& m) {
   // ---------------- text parsing ----------------
-  m.def("textparse_work_words", [](int64_t n) { return psamd::textparse_work_words(n); });
+  m.def("textparse_work_words", [](int64_t n, int fmt) {
+    return psamd::textparse_work_words(n, fmt);
+  }, py::arg("n"), py::arg("fmt") = psamd::kFmtLibsvm);
   m.def("textparse", [](Tensor text, int64_t n, int fmt, uint64_t hash_mod, int64_t row0,
                         int64_t nnz0, Tensor labels, Tensor row_ptr, Tensor keys,
-                        optional<Tensor> vals, Tensor hdr, Tensor work) {
+                        optional<Tensor> vals, optional<Tensor> slots, Tensor hdr, Tensor work) {
     chk(text, at::kByte, "text");
     chk(labels, at::kFloat, "labels");
     chk(row_ptr, at::kLong, "row_ptr");
@@ -56,66 +56,21 @@ void psamd_bind::register_prep(py::module_& m) {
     chk(hdr, at::kInt, "hdr");
     chk(work, at::kInt, "work");
     float* vp = optr<float>(vals, at::kFloat, "vals");
+    int32_t* sp = optr<int32_t>(slots, at::kInt, "slots");
     check(n >= 1 && n <= text.numel(), "textparse: n outside the text buffer");
     check(row0 >= 0 && nnz0 >= 0 && row0 < row_ptr.numel(), "textparse: bad base offsets");
     check(hdr.numel() >= 8, "textparse: header needs 8 words");
-    check(work.numel() >= psamd::textparse_work_words(n), "textparse: work buffer too small");
-    int64_t cap_nnz = keys.numel();
-    if (vp) cap_nnz = std::min<int64_t>(cap_nnz, vals->numel());
-    psamd::textparse(ptr<uint8_t>(text), n, fmt, hash_mod, row0, nnz0, ptr<float>(labels),
-                     labels.numel(), ptr<int64_t>(row_ptr), row_ptr.numel(), ptr<uint64_t>(keys),
-                     vp, cap_nnz, ptr<int32_t>(hdr), ptr<int32_t>(work), cur_stream());
-  }, py::arg("text"), py::arg("n"), py::arg("fmt"), py::arg("hash_mod"), py::arg("row0"),
-     py::arg("nnz0"), py::arg("labels"), py::arg("row_ptr"), py::arg("keys"), py::arg("vals"),
-     py::arg("hdr"), py::arg("work"));
-  m.def("pstext_work_words", [](int64_t n) { return psamd::pstext_work_words(n); });
-  m.def("pstext", [](Tensor text, int64_t n, int fmt, uint64_t hash_mod, int64_t row0,
-                     int64_t nnz0, Tensor labels, Tensor row_ptr, Tensor keys,
-                     optional<Tensor> vals, optional<Tensor> slots, Tensor hdr, Tensor work) {
-    chk(text, at::kByte, "text");
-    chk(labels, at::kFloat, "labels");
-    chk(row_ptr, at::kLong, "row_ptr");
-    chk(keys, at::kLong, "keys");
-    chk(hdr, at::kInt, "hdr");
-    chk(work, at::kInt, "work");
-    float* vp = optr<float>(vals, at::kFloat, "vals");
-    int32_t* sp = optr<int32_t>(slots, at::kInt, "slots");
-    check(n >= 1 && n <= text.numel(), "pstext: n outside the text buffer");
-    check(row0 >= 0 && nnz0 >= 0 && row0 < row_ptr.numel(), "pstext: bad base offsets");
-    check(hdr.numel() >= 8, "pstext: header needs 8 words");
-    check(work.numel() >= psamd::pstext_work_words(n), "pstext: work buffer too small");
+    check(work.numel() >= psamd::textparse_work_words(n, fmt), "textparse: work buffer too small");
     int64_t cap_nnz = keys.numel();
     if (vp) cap_nnz = std::min<int64_t>(cap_nnz, vals->numel());
     if (sp) cap_nnz = std::min<int64_t>(cap_nnz, slots->numel());
-    psamd::pstext(ptr<uint8_t>(text), n, fmt, hash_mod, row0, nnz0, ptr<float>(labels),
-                  labels.numel(), ptr<int64_t>(row_ptr), row_ptr.numel(), ptr<uint64_t>(keys), vp,
-                  sp, cap_nnz, ptr<int32_t>(hdr), ptr<int32_t>(work), cur_stream());
+    psamd::textparse(ptr<uint8_t>(text), n, fmt, hash_mod,
+                     {ptr<float>(labels), labels.numel(), ptr<int64_t>(row_ptr), row_ptr.numel(),
+                      ptr<uint64_t>(keys), vp, sp, cap_nnz, row0, nnz0, ptr<int32_t>(hdr)},
+                     ptr<int32_t>(work), cur_stream());
   }, py::arg("text"), py::arg("n"), py::arg("fmt"), py::arg("hash_mod"), py::arg("row0"),
      py::arg("nnz0"), py::arg("labels"), py::arg("row_ptr"), py::arg("keys"), py::arg("vals"),
      py::arg("slots"), py::arg("hdr"), py::arg("work"));
-  m.def("adtext_work_words", [](int64_t n) { return psamd::adtext_work_words(n); });
-  m.def("adtext", [](Tensor text, int64_t n, int fmt, uint64_t hash_mod, int64_t row0,
-                     int64_t nnz0, Tensor labels, Tensor row_ptr, Tensor keys,
-                     optional<Tensor> slots, Tensor hdr, Tensor work) {
-    chk(text, at::kByte, "text");
-    chk(labels, at::kFloat, "labels");
-    chk(row_ptr, at::kLong, "row_ptr");
-    chk(keys, at::kLong, "keys");
-    chk(hdr, at::kInt, "hdr");
-    chk(work, at::kInt, "work");
-    int32_t* sp = optr<int32_t>(slots, at::kInt, "slots");
-    check(n >= 1 && n <= text.numel(), "adtext: n outside the text buffer");
-    check(row0 >= 0 && nnz0 >= 0 && row0 < row_ptr.numel(), "adtext: bad base offsets");
-    check(hdr.numel() >= 8, "adtext: header needs 8 words");
-    check(work.numel() >= psamd::adtext_work_words(n), "adtext: work buffer too small");
-    int64_t cap_nnz = keys.numel();
-    if (sp) cap_nnz = std::min<int64_t>(cap_nnz, slots->numel());
-    psamd::adtext(ptr<uint8_t>(text), n, fmt, hash_mod, row0, nnz0, ptr<float>(labels),
-                  labels.numel(), ptr<int64_t>(row_ptr), row_ptr.numel(), ptr<uint64_t>(keys), sp,
-                  cap_nnz, ptr<int32_t>(hdr), ptr<int32_t>(work), cur_stream());
-  }, py::arg("text"), py::arg("n"), py::arg("fmt"), py::arg("hash_mod"), py::arg("row0"),
-     py::arg("nnz0"), py::arg("labels"), py::arg("row_ptr"), py::arg("keys"), py::arg("slots"),
-     py::arg("hdr"), py::arg("work"));
   m.def("textparse_rebase", [](Tensor in, Tensor out, int64_t n, int64_t delta) {
     chk(in, at::kLong, "in");
     chk(out, at::kLong, "out");

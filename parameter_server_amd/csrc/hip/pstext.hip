@@ -38,17 +38,11 @@
 // Safety on arbitrary bytes as in textparse.hip: reads clamped to n, sizes from the count
 // pass and checked before anything is emitted (sticky H_CAP), every emitted index guarded,
 // every token loop bounded by textnum::kMaxTok + 1.
-#include "pstext.h"
 #include "textparse.cuh"
-#include "../core/textnum.h"
-
-#include <stdexcept>
 
 namespace psamd {
 
 namespace {
-
-constexpr int kFmtSparse = 2, kFmtSparseBinary = 3;  // data.TEXT_FORMATS
 
 // per-span summary (ps_count -> ps_scan) and per-span bases (ps_scan -> ps_emit)
 enum { S_NTOK, S_NLAB, S_NHEAD, S_AMB, S_FN, S_WORDS = 8 };
@@ -249,18 +243,14 @@ __global__ void __launch_bounds__(kTpBlk) ps_emit_kernel(
     const int i = __ffs((int)r) - 1;
     r &= r - 1;
     const int off = threadIdx.x * kTpBytes + i;
-    const int64_t g = base + off;
     const bool is_lab = (t.lab >> i) & 1u, is_head = (t.head >> i) & 1u;
     if (is_lab) ++L;
     if (is_head) ++Hd;
     const int64_t R = L - 1;         // this token's row
     const int64_t pos = T - L - Hd;  // a feature token's index among the features
     ++T;
-    // the token's bytes: LDS when kMaxTok + 1 bytes from its start stay inside the span
-    // (bytes past n read as '\n' there), else global memory clamped to n
-    const int64_t left = n - g;
-    const int lim = (int)(left < textnum::kMaxTok + 1 ? left : textnum::kMaxTok + 1);
-    const uint8_t* p = off + textnum::kMaxTok + 1 <= kTpSpan ? lds_text + off : text + g;
+    int lim;
+    const uint8_t* p = tp_token_window(text, n, base, off, lds_text, &lim);
     int len = 0, colon = -1, ncolon = 0;
     for (; len < lim; ++len) {
       const uint32_t c = p[len];
@@ -312,14 +302,7 @@ __global__ void __launch_bounds__(kTpBlk) ps_emit_kernel(
     bad += st == textnum::kBad;
     defer += st == textnum::kDefer;
   }
-  // per-workgroup reduction; the header is touched only when there is something to add
-  const int nbad = __syncthreads_count(bad), ndef = __syncthreads_count(defer);
-  const int any_nu = __syncthreads_or(nonunit);
-  if (threadIdx.x == 0) {
-    if (nbad) atomicAdd(&hdr[H_BAD], nbad);
-    if (ndef) atomicAdd(&hdr[H_DEFER], ndef);
-    if (any_nu && !__atomic_load_n(&hdr[H_NONUNIT], __ATOMIC_RELAXED)) atomicOr(&hdr[H_NONUNIT], 1);
-  }
+  tp_report(bad, defer, nonunit, hdr);
 }
 
 // slots[j]: the ordinal of feature j's group -> the value of that group's head.
@@ -343,43 +326,31 @@ inline int64_t ps_cap_groups(int64_t n) { return n / 2 + 2; }  // (a head every 
 
 }  // namespace
 
-int64_t pstext_work_words(int64_t n) {
+int64_t ps_work_words(int64_t n) {
   return ((n + kTpSpan - 1) / kTpSpan) * (S_WORDS + B_WORDS) + A_WORDS + ps_cap_groups(n);
 }
 
-// text: n bytes, 16-byte aligned. Outputs behind row0 rows / nnz0 features already in the
-// buffers. hdr: H_WORDS int32 (H_CAP must be cleared by the caller before the first use);
-// work: pstext_work_words(n) int32.
-void pstext(const uint8_t* text, int64_t n, int fmt, uint64_t hash_mod, int64_t row0,
-            int64_t nnz0, float* labels, int64_t cap_rows, int64_t* row_ptr, int64_t cap_rp,
-            uint64_t* keys, float* vals, int32_t* slots, int64_t cap_nnz, int32_t* hdr,
-            int32_t* work, hipStream_t st) {
-  if (fmt != kFmtSparse && fmt != kFmtSparseBinary)
-    throw std::invalid_argument("pstext: no device parser for this text format");
-  if (n <= 0 || n > ((int64_t)1 << 30))
-    throw std::invalid_argument("pstext: chunk size must be in [1, 2^30] bytes");
-  if (((uintptr_t)text & 15) != 0)
-    throw std::invalid_argument("pstext: text buffer must be 16-byte aligned");
-  if (fmt == kFmtSparse && !vals) throw std::invalid_argument("pstext: SPARSE needs vals");
+// Behind textparse()'s checks (textparse.hip). valued: SPARSE, else SPARSE_BINARY.
+void ps_launch(const uint8_t* text, int64_t n, bool valued, uint64_t hash_mod, const TextOut& o,
+               int32_t* work, hipStream_t st) {
   const int64_t nb = (n + kTpSpan - 1) / kTpSpan;
   int32_t* sum = work;
   int32_t* bases = work + nb * S_WORDS;
   int32_t* aux = bases + nb * B_WORDS;
   int32_t* group_slot = aux + A_WORDS;
   const int64_t cap_groups = ps_cap_groups(n);
-  const int fgrid = grid_for(n / 8 + 1, 256, 2048);
   ps_count_kernel<<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, sum);
-  ps_scan_kernel<<<1, kTpBlk, 0, st>>>(sum, bases, nb, row0, nnz0, cap_rows, cap_rp, cap_nnz,
-                                    row_ptr, aux, hdr);
-  const auto emit = fmt == kFmtSparse ? (slots ? ps_emit_kernel<true, true> : ps_emit_kernel<true, false>)
-                                      : (slots ? ps_emit_kernel<false, true> : ps_emit_kernel<false, false>);
-  emit<<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, bases, row0, nnz0, cap_rows, cap_nnz, labels,
-                                        row_ptr, keys, vals, slots, group_slot, cap_groups, hdr);
-  if (slots)
-    ps_gather_kernel<<<fgrid, 256, 0, st>>>(slots, nnz0, group_slot, cap_groups, aux, hdr);
-  tp_finish_kernel<<<fgrid, 256, 0, st>>>(keys, row_ptr, row0, nnz0, false, hdr);
-  if (hash_mod) tp_mod_kernel<<<fgrid, 256, 0, st>>>(keys, nnz0, hash_mod, hdr);
-  PSAMD_HIP_CHECK(hipGetLastError());
+  ps_scan_kernel<<<1, kTpBlk, 0, st>>>(sum, bases, nb, o.row0, o.nnz0, o.cap_rows, o.cap_rp,
+                                    o.cap_nnz, o.row_ptr, aux, o.hdr);
+  const auto emit = valued ? (o.slots ? ps_emit_kernel<true, true> : ps_emit_kernel<true, false>)
+                           : (o.slots ? ps_emit_kernel<false, true> : ps_emit_kernel<false, false>);
+  emit<<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, bases, o.row0, o.nnz0, o.cap_rows, o.cap_nnz,
+                                        o.labels, o.row_ptr, o.keys, o.vals, o.slots, group_slot,
+                                        cap_groups, o.hdr);
+  if (o.slots)
+    ps_gather_kernel<<<tp_fgrid(n), 256, 0, st>>>(o.slots, o.nnz0, group_slot, cap_groups, aux,
+                                                  o.hdr);
+  tp_finish(o, n, false, hash_mod, st);
 }
 
 }  // namespace psamd

@@ -1,12 +1,16 @@
-// What the device text parsers (textparse.hip, pstext.hip) share: the work decomposition
-// (16 KiB of text per 1024-thread workgroup), the header words, the associative carries and
-// the workgroup scan over them, the clamped load of a span into LDS, the header / capacity
-// step that closes a scan launch, and the finish launches (row-width range with the
-// optional LIBSVM order check, keys mod hash_mod). Each parser adds its own classify,
-// count, scan and emit kernels (they know the grammar). Included by .hip files only;
+// What the device text parsers (textparse.hip, pstext.hip, adtext.hip) share: the work
+// decomposition (16 KiB of text per 1024-thread workgroup), the header words, the
+// associative carries and the workgroup scan over them, the clamped load of a span into LDS,
+// the header / capacity step that closes a scan launch, the bytes an emit thread reads a
+// token from, the reduction that closes an emit launch, and the finish launches (row-width
+// range with the optional LIBSVM order check, keys mod hash_mod). Each parser adds its own
+// classify, count, scan and emit kernels (they know the grammar). The host side of the
+// finish launches (tp_fgrid, tp_finish) is here as well. Included by .hip files only;
 // everything has internal linkage.
 #pragma once
 #include "common.cuh"
+#include "textparse.h"
+#include "../core/textnum.h"
 
 #include <cstdint>
 
@@ -113,6 +117,32 @@ __device__ __forceinline__ void tp_write_header(int64_t rows, int64_t nnz, uint3
   else if (row_ptr) row_ptr[row0 + rows] = nnz0 + nnz;  // (model lines keep no offsets)
 }
 
+// The bytes of the token that starts at byte off of the span at base, and through *lim how
+// many of them may be read: LDS when kMaxTok + 1 bytes from its start stay inside the span
+// (bytes past n read as '\n' there), else global memory clamped to n.
+__device__ __forceinline__ const uint8_t* tp_token_window(const uint8_t* __restrict__ text,
+                                                          int64_t n, int64_t base, int off,
+                                                          const uint8_t* lds_text, int* lim) {
+  const int64_t left = n - (base + off);
+  *lim = (int)(left < textnum::kMaxTok + 1 ? left : textnum::kMaxTok + 1);
+  return off + textnum::kMaxTok + 1 <= kTpSpan ? lds_text + off : text + (base + off);
+}
+
+// Closes an emit launch: the per-workgroup reduction of the threads' bad / deferred tokens
+// and "a value differs from 1" (kNonunit: the format has values); the header is touched only
+// when there is something to add.
+template <bool kNonunit = true>
+__device__ __forceinline__ void tp_report(int bad, int defer, int nonunit,
+                                          int32_t* __restrict__ hdr) {
+  const int nbad = __syncthreads_count(bad), ndef = __syncthreads_count(defer);
+  const int any_nu = kNonunit ? __syncthreads_or(nonunit) : 0;
+  if (threadIdx.x == 0) {
+    if (nbad) atomicAdd(&hdr[H_BAD], nbad);
+    if (ndef) atomicAdd(&hdr[H_DEFER], ndef);
+    if (any_nu && !__atomic_load_n(&hdr[H_NONUNIT], __ATOMIC_RELAXED)) atomicOr(&hdr[H_NONUNIT], 1);
+  }
+}
+
 // Index order inside a row (LIBSVM) and the row-width range. A descent keys[j-1] > keys[j]
 // is legal only where j starts a row: only descents search row_ptr (<= 40 bounded steps).
 __global__ void __launch_bounds__(256) tp_finish_kernel(const uint64_t* __restrict__ keys,
@@ -174,6 +204,17 @@ __global__ void __launch_bounds__(256) tp_mod_kernel(uint64_t* __restrict__ keys
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nnz;
        j += (int64_t)gridDim.x * blockDim.x)
     keys[nnz0 + j] %= mod;
+}
+
+inline int tp_fgrid(int64_t n) { return grid_for(n / 8 + 1, 256, 2048); }
+
+// The launches that close every parser: tp_finish, then tp_mod when hash_mod is given.
+inline void tp_finish(const TextOut& o, int64_t n, bool check_order, uint64_t hash_mod,
+                      hipStream_t st) {
+  const int fgrid = tp_fgrid(n);
+  tp_finish_kernel<<<fgrid, 256, 0, st>>>(o.keys, o.row_ptr, o.row0, o.nnz0, check_order, o.hdr);
+  if (hash_mod) tp_mod_kernel<<<fgrid, 256, 0, st>>>(o.keys, o.nnz0, hash_mod, o.hdr);
+  PSAMD_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace

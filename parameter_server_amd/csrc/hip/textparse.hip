@@ -33,9 +33,7 @@
 // '\n'), every output size comes from the counting pass and is checked against the
 // capacities before anything is emitted (sticky H_CAP), every emitted index is guarded,
 // and every loop over a token is bounded by textnum::kMaxTok + 1.
-#include "textparse.h"
 #include "textparse.cuh"
-#include "../core/textnum.h"
 
 #include <stdexcept>
 #include <string>
@@ -44,7 +42,6 @@ namespace psamd {
 
 namespace {
 
-constexpr int kFmtLibsvm = 5, kFmtCriteo = 8;  // data.TEXT_FORMATS
 // Internal: key<TAB>weight model lines (modeltext_parse below; not a data.TEXT_FORMATS id).
 // Tokens as in LIBSVM; a row is a key token and its weight token, nothing else.
 constexpr int kFmtModel = 100;
@@ -275,11 +272,8 @@ __global__ void __launch_bounds__(kTpBlk) tp_emit_kernel(
     const int64_t R = L - 1;              // this token's row
     const int64_t pos = T - L;            // a feature token's index among the features
     ++T;
-    // the token's bytes: LDS when kMaxTok + 1 bytes from its start stay inside the span
-    // (bytes past n read as '\n' there), else global memory clamped to n
-    const int64_t left = n - g;
-    const int lim = (int)(left < textnum::kMaxTok + 1 ? left : textnum::kMaxTok + 1);
-    const uint8_t* p = off + textnum::kMaxTok + 1 <= kTpSpan ? lds_text + off : text + g;
+    int lim;
+    const uint8_t* p = tp_token_window(text, n, base, off, lds_text, &lim);
     int len = 0, colon = -1;
     for (; len < lim; ++len) {
       const uint32_t c = p[len];
@@ -387,57 +381,62 @@ __global__ void __launch_bounds__(kTpBlk) tp_emit_kernel(
     bad += st == textnum::kBad;
     defer += st == textnum::kDefer;
   }
-  // per-workgroup reduction; the header is touched only when there is something to add
-  const int nbad = __syncthreads_count(bad), ndef = __syncthreads_count(defer);
-  const int any_nu = __syncthreads_or(nonunit);
-  if (threadIdx.x == 0) {
-    if (nbad) atomicAdd(&hdr[H_BAD], nbad);
-    if (ndef) atomicAdd(&hdr[H_DEFER], ndef);
-    if (any_nu && !__atomic_load_n(&hdr[H_NONUNIT], __ATOMIC_RELAXED)) atomicOr(&hdr[H_NONUNIT], 1);
+  tp_report(bad, defer, nonunit, hdr);
+}
+
+template <int kFmt>
+void tp_launch(const uint8_t* text, int64_t n, uint64_t hash_mod, const TextOut& o, int32_t* work,
+               hipStream_t st) {
+  const int64_t nb = (n + kTpSpan - 1) / kTpSpan;
+  int32_t* sum = work;
+  int32_t* bases = work + nb * S_WORDS;
+  tp_count_kernel<kFmt><<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, sum);
+  tp_scan_kernel<<<1, kTpBlk, 0, st>>>(sum, bases, nb, o.row0, o.nnz0, o.cap_rows, o.cap_rp,
+                                    o.cap_nnz, o.row_ptr, o.hdr);
+  tp_emit_kernel<kFmt><<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, bases, o.row0, o.nnz0, o.cap_rows,
+                                                       o.cap_nnz, o.labels, o.row_ptr, o.keys,
+                                                       o.vals, o.hdr);
+  tp_finish(o, n, kFmt == kFmtLibsvm, hash_mod, st);
+}
+
+// The kernel family of a text format (the .hip file with its kernels); throws for a format
+// without a device parser.
+enum { kFamTp, kFamPs, kFamAd };
+int family_of(int fmt) {
+  switch (fmt) {
+    case kFmtLibsvm: case kFmtCriteo: return kFamTp;
+    case kFmtSparse: case kFmtSparseBinary: return kFamPs;
+    case kFmtAdfea: case kFmtTerafea: return kFamAd;
   }
+  throw std::invalid_argument("textparse: no device parser for this text format");
 }
 
 }  // namespace
 
 int64_t textparse_span() { return kTpSpan; }
-int64_t textparse_work_words(int64_t n) {
-  return ((n + kTpSpan - 1) / kTpSpan) * (S_WORDS + B_WORDS) + 16;
+int64_t textparse_work_words(int64_t n, int fmt) {
+  switch (family_of(fmt)) {
+    case kFamTp: return ((n + kTpSpan - 1) / kTpSpan) * (S_WORDS + B_WORDS) + 16;
+    case kFamPs: return ps_work_words(n);
+    default: return ad_work_words(n);
+  }
 }
 
-// text: n bytes, 16-byte aligned. Outputs behind row0 rows / nnz0 features already in the
-// buffers. hdr: H_WORDS int32 (H_CAP must be cleared by the caller before the first use);
-// work: textparse_work_words(n) int32. vals may be null for CRITEO.
-void textparse(const uint8_t* text, int64_t n, int fmt, uint64_t hash_mod, int64_t row0,
-               int64_t nnz0, float* labels, int64_t cap_rows, int64_t* row_ptr, int64_t cap_rp,
-               uint64_t* keys, float* vals, int64_t cap_nnz, int32_t* hdr, int32_t* work,
-               hipStream_t st) {
-  if (fmt != kFmtLibsvm && fmt != kFmtCriteo)
-    throw std::invalid_argument("textparse: no device parser for this text format");
+// The one entry of the six device parsers: the argument checks, then the format's launcher
+// (here, pstext.hip, adtext.hip).
+void textparse(const uint8_t* text, int64_t n, int fmt, uint64_t hash_mod, const TextOut& out,
+               int32_t* work, hipStream_t st) {
+  const int family = family_of(fmt);
   if (n <= 0 || n > ((int64_t)1 << 30))
     throw std::invalid_argument("textparse: chunk size must be in [1, 2^30] bytes");
   if (((uintptr_t)text & 15) != 0)
     throw std::invalid_argument("textparse: text buffer must be 16-byte aligned");
-  if (fmt == kFmtLibsvm && !vals) throw std::invalid_argument("textparse: LIBSVM needs vals");
-  const int64_t nb = (n + kTpSpan - 1) / kTpSpan;
-  int32_t* sum = work;
-  int32_t* bases = work + nb * S_WORDS;
-  const int fgrid = grid_for(n / 8 + 1, 256, 2048);
-  if (fmt == kFmtLibsvm) {
-    tp_count_kernel<kFmtLibsvm><<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, sum);
-    tp_scan_kernel<<<1, kTpBlk, 0, st>>>(sum, bases, nb, row0, nnz0, cap_rows, cap_rp, cap_nnz,
-                                      row_ptr, hdr);
-    tp_emit_kernel<kFmtLibsvm><<<(unsigned)nb, kTpBlk, 0, st>>>(
-        text, n, bases, row0, nnz0, cap_rows, cap_nnz, labels, row_ptr, keys, vals, hdr);
-  } else {
-    tp_count_kernel<kFmtCriteo><<<(unsigned)nb, kTpBlk, 0, st>>>(text, n, sum);
-    tp_scan_kernel<<<1, kTpBlk, 0, st>>>(sum, bases, nb, row0, nnz0, cap_rows, cap_rp, cap_nnz,
-                                      row_ptr, hdr);
-    tp_emit_kernel<kFmtCriteo><<<(unsigned)nb, kTpBlk, 0, st>>>(
-        text, n, bases, row0, nnz0, cap_rows, cap_nnz, labels, row_ptr, keys, vals, hdr);
-  }
-  tp_finish_kernel<<<fgrid, 256, 0, st>>>(keys, row_ptr, row0, nnz0, fmt == kFmtLibsvm, hdr);
-  if (hash_mod) tp_mod_kernel<<<fgrid, 256, 0, st>>>(keys, nnz0, hash_mod, hdr);
-  PSAMD_HIP_CHECK(hipGetLastError());
+  if ((fmt == kFmtLibsvm || fmt == kFmtSparse) && !out.vals)
+    throw std::invalid_argument("textparse: LIBSVM and SPARSE need vals");
+  if (family == kFamPs) return ps_launch(text, n, fmt == kFmtSparse, hash_mod, out, work, st);
+  if (family == kFamAd) return ad_launch(text, n, fmt == kFmtAdfea, hash_mod, out, work, st);
+  if (fmt == kFmtLibsvm) return tp_launch<kFmtLibsvm>(text, n, hash_mod, out, work, st);
+  return tp_launch<kFmtCriteo>(text, n, hash_mod, out, work, st);
 }
 
 // key<TAB>weight model text (utils/checkpoint.py): keys[r] / w[r] of line r, in file order.

@@ -25,9 +25,8 @@ device slots; ``release(batch)`` after the step that reads it was issued):
   a multi-rank app agrees on its step count once instead of every step.
 
 The text source has two parsers (``parser=``). ``"cpu"`` (the default) is the path above.
-``"gpu"`` parses LIBSVM / CRITEO text (ops/textparse.py, textparse.hip) and the slot-grouped
-SPARSE_BINARY / SPARSE text of the CTR confs (ops/pstext.py, pstext.hip) and ADFEA text
-(ops/adtext.py, adtext.hip) on the device:
+``"gpu"`` parses LIBSVM / CRITEO text (textparse.hip), the slot-grouped SPARSE_BINARY / SPARSE
+text of the CTR confs (pstext.hip) and ADFEA text (adtext.hip) on the device (ops/textparse.py):
 reader threads read each file straight into pinned chunk buffers of ``chunk_bytes``, cut at
 the last newline; a chunk is copied to HBM on the copy stream and parsed on a parse stream
 into one of a ring of device output buffers; minibatches are slices of the parsed chunk
@@ -36,7 +35,7 @@ that span files: rows left over are carried to the front of the next chunk's out
 device-to-device copy). A chunk the kernels decline (a malformed or ``#`` line, a number
 outside their exact domain, a line longer than a chunk) is parsed by the CPU parser from
 the pinned copy of the same bytes (``deferred_chunks``). TERAFEA has a device parser
-(ops/adtext.py, used by ``SlotReader``) but stays on the CPU parser here for now. Other
+(the same entry, used by ``SlotReader``) but stays on the CPU parser here for now. Other
 formats, ``max_lines_per_file > 0`` and ``device="cpu"`` use the CPU parser whatever ``parser``
 says; ``"auto"`` picks the GPU parser where it applies.
 
@@ -56,7 +55,7 @@ import torch
 
 from . import TEXT_FORMATS, ExampleBatch, StreamReader, read_file
 from . import bincache
-from ..ops import adtext, pstext, textparse
+from ..ops import textparse
 
 
 @dataclass
@@ -166,11 +165,12 @@ class DeviceFeeder:
         self._fmt_id = TEXT_FORMATS.get(fmt, 0) if isinstance(fmt, str) else int(fmt)
         # the parser in use: the device parser needs a GPU, a format it knows and whole files
         self.parser = "gpu" if (parser != "cpu" and self.gpu and max_lines_per_file <= 0
-                                and (textparse.supported(self._fmt_id)
-                                     # (group heads are validated only when slots are kept)
-                                     or (pstext.supported(self._fmt_id) and ignore_slot)
-                                     # (TERAFEA keeps the CPU parser in the feeder)
-                                     or (self._fmt_id == TEXT_FORMATS["ADFEA"] and ignore_slot))
+                                and textparse.supported(self._fmt_id)
+                                # (TERAFEA keeps the CPU parser in the feeder)
+                                and self._fmt_id != TEXT_FORMATS["TERAFEA"]
+                                # (minibatches carry no slot ids, and group heads are
+                                # validated only when slots are kept)
+                                and (ignore_slot or not textparse.produces_slots(self._fmt_id))
                                 ) else "cpu"
         self.chunk_bytes = max(1024, int(chunk_bytes))
         self.text_chunks = 0      # chunks of text handed to the device parser
@@ -477,9 +477,7 @@ class DeviceFeeder:
                 return it
 
             # (the formats whose chunks keep a value per feature; the others are binary)
-            valued = self._fmt_id in (TEXT_FORMATS["LIBSVM"], TEXT_FORMATS["SPARSE"])
-            grouped = pstext.supported(self._fmt_id)
-            adlog = adtext.supported(self._fmt_id)
+            valued = self._fmt_id in textparse._VALUED_FORMATS
             carry = None     # rows parsed but not yet cut into a minibatch
             pieces = []      # host copies of the current file's arrays (cache_dir)
             nxt = fetch()
@@ -512,22 +510,16 @@ class DeviceFeeder:
                     if cur[0] == "chunk":
                         _, i, n, f, d, ev = cur
                         ps.wait_event(ev)
-                        if grouped or adlog:  # (minibatches carry no slot ids: groups are not read)
-                            parse = adtext.parse_ad_text_device if adlog else \
-                                pstext.parse_ps_text_device
-                            res = parse(
-                                d, self._fmt_id, self.num_features, ignore_slot=True, out=st,
-                                row0=r0, nnz0=n0, n=n, host=tp["pin"][i])
-                        else:
-                            res = textparse.parse_text_device(
-                                d, self._fmt_id, self.num_features, out=st, row0=r0, nnz0=n0,
-                                n=n, host=tp["pin"][i])
+                        # (minibatches carry no slot ids: groups are not read)
+                        res = textparse.parse_text_device(
+                            d, self._fmt_id, self.num_features, ignore_slot=True, out=st,
+                            row0=r0, nnz0=n0, n=n, host=tp["pin"][i])
                         free_pin.put(i)
                     else:  # a line longer than a chunk: the CPU parser's
                         n = len(cur[1])
                         res = textparse._store_host(
-                            textparse._host_parse(cur[1], self._fmt_id, self.num_features), st,
-                            r0, n0, self._fmt_id, True)
+                            textparse._host_parse(cur[1], self._fmt_id, self.num_features, True),
+                            st, r0, n0, self._fmt_id, True)
                     self.bytes_text += n
                     self.deferred_chunks += bool(res.deferred)
                     Rn, N = r0 + res.rows, n0 + res.nnz

@@ -12,8 +12,8 @@ Here files are parsed by the C++ runtime (``_pscore.parse_text``), the cache is
 slot info follows the reference ``InfoParser`` (src/data/info_parser.cc:10-48):
 ``max_key`` is exclusive (max + 1), label slot 0 has range [0, 1).
 
-``parser="gpu"`` with a GPU ``device`` parses SPARSE_BINARY / SPARSE files (ops/pstext.py)
-and ADFEA / TERAFEA files (ops/adtext.py) on the device on a cache miss (<= 32 MiB chunks
+``parser="gpu"`` with a GPU ``device`` parses SPARSE_BINARY / SPARSE and ADFEA / TERAFEA
+files (ops/textparse.py) on the device on a cache miss (<= 32 MiB chunks
 cut at a newline, slot ids included); the arrays come back as an ``ExampleBatch`` and go through the same split and cache. Other
 formats, ``.gz`` / ``hdfs://`` paths and CPU devices stay on the host parser, and so does
 ``parser="auto"``: with the split by slot on the host, which then bounds the load, the device
@@ -139,11 +139,13 @@ class SlotReader:
         self.nthreads = max(1, nthreads)
         self.hit_cache = 0
         self.device = device
+        from ..ops.textparse import produces_slots
+
         # the parser in use: the device parser needs a GPU and a format it knows. "auto" stays
         # on the host: the load is bound by the split by slot on the host, and the device
         # route measured no faster (benchmarks/bench_slotreader.py)
         self.parser = "gpu" if (parser == "gpu" and _is_gpu_device(device)
-                                and _ps_supported(fmt)) else "cpu"
+                                and produces_slots(fmt)) else "cpu"
         self.deferred_chunks = 0  # device route: chunks the host parser took after all
         # the split by slot in use: on the device only behind the device parser
         self.split = "device" if split == "device" and self.parser == "gpu" else "host"
@@ -243,8 +245,7 @@ class SlotReader:
         import torch
 
         from ..ops.slotsplit import split_by_slot
-
-        parse = _device_parser(self.fmt)
+        from ..ops.textparse import parse_text_device
 
         with open(path, "rb") as f:
             chunks = self._text_chunks(f.read())
@@ -253,7 +254,7 @@ class SlotReader:
         parts, nonunit = [], False
         for host in chunks:
             with torch.cuda.device(self.device):
-                res = parse(
+                res = parse_text_device(
                     torch.frombuffer(bytearray(host), dtype=torch.uint8).to(self.device), self.fmt,
                     ignore_slot=self.ignore_slot, host=host)
                 self.deferred_chunks += bool(res.deferred)
@@ -282,13 +283,14 @@ class SlotReader:
         """One plain file through the device parser, chunk by chunk, as an ExampleBatch."""
         import torch
 
-        parse = _device_parser(self.fmt)
+        from ..ops.textparse import parse_text_device
+
         with open(path, "rb") as f:
             raw = f.read()
         parts = []
         for host in self._text_chunks(raw):
             with torch.cuda.device(self.device):
-                res = parse(
+                res = parse_text_device(
                     torch.frombuffer(bytearray(host), dtype=torch.uint8).to(self.device), self.fmt,
                     ignore_slot=self.ignore_slot, host=host)
                 self.deferred_chunks += bool(res.deferred)
@@ -375,20 +377,6 @@ def _is_gpu_device(device) -> bool:
     import torch
 
     return torch.device(device).type == "cuda"
-
-
-def _ps_supported(fmt) -> bool:
-    """Whether a device parser that keeps slot ids knows ``fmt``."""
-    from ..ops import adtext, pstext
-
-    return pstext.supported(fmt) or adtext.supported(fmt)
-
-
-def _device_parser(fmt):
-    """The device parser of ``fmt`` (ops/pstext.py and ops/adtext.py share one signature)."""
-    from ..ops import adtext, pstext
-
-    return adtext.parse_ad_text_device if adtext.supported(fmt) else pstext.parse_ps_text_device
 
 
 def _jsonable(info: dict) -> dict:

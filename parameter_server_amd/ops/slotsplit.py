@@ -2,9 +2,9 @@
 ``SlotData.from_batch`` makes of a CSR batch with per-feature slot ids, on the device
 (``slotsplit.hip``) for GPU tensors and by a stable sort for CPU tensors.
 
-The device path is a strict fast path with the contract of ops/textparse.py and
-ops/pstext.py: a chunk the kernels decide is split entirely by them; a chunk that names
-more than ``max_ids()`` groups or a group id outside [0, 2^31) (cause ``"ids"``), whose
+The device path is a strict fast path with the contract of ops/textparse.py: a chunk the
+kernels decide is split entirely by them; a chunk that names more than ``max_ids()``
+groups or a group id outside [0, 2^31) (cause ``"ids"``), whose
 ``S * (R + 1)`` cells exceed the cell cap (``"cells"``) or in which a row names a group
 twice (``"repeat"``: the stable order of two runs cannot be had from unordered atomics) is
 copied back, split by ``SlotData.from_batch`` and uploaded -- the caller sees the same

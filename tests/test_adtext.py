@@ -1,8 +1,8 @@
-"""The CPU side of the ADFEA / TERAFEA text parser (ops/adtext.py): which formats it claims
-(and that the two earlier device parsers claim what they claimed), the host route of
-``parse_ad_text_device`` (CPU buffers and bytes; the slot ids come from the host batch),
-``SlotReader`` staying on the host route without a GPU, and ``write_text`` writing both
-formats so that the host parser gives the groups back."""
+"""The CPU side of the ADFEA / TERAFEA text parser (ops/textparse.py; ops/adtext.py keeps its
+earlier names): which formats it claims (and what the one table says of all eight names),
+the host route of ``parse_ad_text_device`` (CPU buffers and bytes; the slot ids come from the
+host batch), ``SlotReader`` staying on the host route without a GPU, and ``write_text``
+writing both formats so that the host parser gives the groups back."""
 import numpy as np
 import pytest
 import torch
@@ -25,11 +25,18 @@ def test_supported_formats():
     assert [data.TEXT_FORMATS[f] for f in NAMES] == list(range(1, 9))
     for f in ("ADFEA", "TERAFEA", 4, 6):
         assert adtext.supported(f)
-    for f in ("DENSE", "SPARSE", "SPARSE_BINARY", "LIBSVM", "VW", "CRITEO", 1, 2, 3, 5, 7, 8):
-        assert not adtext.supported(f)
-    # the two earlier parsers claim what they claimed, by name and by id
+        assert textparse.supported(f) and textparse.produces_slots(f)
+        assert textparse.traits(f).family == "adtext" and not textparse.traits(f).valued
+    # the one table, by name and by id: every format but DENSE and VW, each in its family
+    family = {"LIBSVM": "textparse", "CRITEO": "textparse", "SPARSE": "pstext",
+              "SPARSE_BINARY": "pstext", "ADFEA": "adtext", "TERAFEA": "adtext"}
     for k, f in enumerate(NAMES, 1):
-        assert textparse.supported(f) == textparse.supported(k) == (f in ("LIBSVM", "CRITEO"))
+        assert textparse.supported(f) == textparse.supported(k) == (f in family)
+        t = textparse.traits(f)
+        assert t == textparse.traits(k) and (t.family if t else None) == family.get(f)
+        assert t is None or t.id == k
+        # the family modules claim what they claimed
+        assert adtext.supported(f) == adtext.supported(k) == (f in ("ADFEA", "TERAFEA"))
         assert pstext.supported(f) == pstext.supported(k) == (f in ("SPARSE", "SPARSE_BINARY"))
 
 

@@ -1,6 +1,7 @@
-"""The CPU side of the slot-grouped text parser (ops/pstext.py): which formats it claims,
-the host route of ``parse_ps_text_device`` (CPU buffers and bytes; the slot ids come from
-the host batch), and ``SlotReader`` staying on the host route without a GPU."""
+"""The CPU side of the slot-grouped text parser (ops/textparse.py; ops/pstext.py keeps its
+earlier names): which formats it claims, the host route of ``parse_ps_text_device`` (CPU
+buffers and bytes; the slot ids come from the host batch), and ``SlotReader`` staying on the
+host route without a GPU."""
 import numpy as np
 import pytest
 import torch
@@ -17,12 +18,21 @@ RAW_V = b"1; 3 5:0.5 6:1; 7 9:-2e-3\n0; 2 4:1\n"
 def test_supported_formats():
     for f in ("SPARSE_BINARY", "SPARSE", 2, 3):
         assert pstext.supported(f)
+        assert textparse.supported(f) and textparse.produces_slots(f)
+        assert textparse.traits(f).family == "pstext"
     for f in ("LIBSVM", "CRITEO", "DENSE", "ADFEA", "TERAFEA", "VW", 1, 4, 5, 6, 7, 8):
         assert not pstext.supported(f)
-    # the LIBSVM / CRITEO parser claims what it claimed
-    assert textparse.supported("LIBSVM") and textparse.supported("CRITEO")
-    assert not any(textparse.supported(f) for f in ("SPARSE", "SPARSE_BINARY", "DENSE",
-                                                    "ADFEA", "TERAFEA", 2, 3))
+    assert textparse.traits("SPARSE").valued and not textparse.traits("SPARSE_BINARY").valued
+    # the one entry claims the six formats with kernels, and no other
+    for f in ("LIBSVM", "CRITEO", "ADFEA", "TERAFEA", 4, 5, 6, 8):
+        assert textparse.supported(f) and textparse.traits(f).family != "pstext"
+    for f in ("DENSE", "VW", 1, 7):
+        assert not textparse.supported(f) and not textparse.produces_slots(f)
+    # LIBSVM / CRITEO have no slot ids to keep
+    for f in ("LIBSVM", "CRITEO"):
+        assert not textparse.produces_slots(f)
+        with pytest.raises(ValueError):
+            textparse.parse_text_device(b"1 2:3\n", f, ignore_slot=False)
 
 
 @pytest.mark.parametrize("ignore_slot", [True, False])

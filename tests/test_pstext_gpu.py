@@ -1,9 +1,10 @@
-"""The device parser of the slot-grouped text formats (pstext.hip, ops/pstext.py) against
+"""The device parser of the slot-grouped text formats (pstext.hip, ops/textparse.py) against
 the host parser on the same bytes: labels, row offsets, keys and slot ids bitwise, values
 bitwise or None by the host's binary rule, bad-line and row counts -- on clean corpora
 (which must not be deferred to the host), at every boundary of the work decomposition, on
 every kind of line the kernels hand back, on random bytes, behind carried rows, through the
 DeviceFeeder, the file-fed app and the SlotReader."""
+import functools
 import os
 import random
 import re
@@ -13,50 +14,16 @@ import pytest
 import torch
 
 from parameter_server_amd import data
-from parameter_server_amd.ops import pstext, textparse
+from parameter_server_amd.ops import textparse
 from parameter_server_amd.ops.native import core
-from parameter_server_amd.ops.pstext import parse_ps_text_device
-from parameter_server_amd.ops.textparse import TextParseBuffers
+from parameter_server_amd.ops.textparse import TextParseBuffers, parse_text_device
+from textparse_cases import _dev, check_against_host
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 SPAN = 16384  # bytes of text per workgroup (textparse.cuh)
 FMTS = ["SPARSE_BINARY", "SPARSE"]
-
-
-def _dev(raw: bytes) -> torch.Tensor:
-    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(DEV) if raw else \
-        torch.empty(0, dtype=torch.uint8, device=DEV)
-
-
-def _check(raw: bytes, fmt: str, hash_mod: int = 0, *, ignore_slot: bool = False,
-           clean: bool = True):
-    """Device result == host result on ``raw``; returns the device result."""
-    ref = data.parse_text(raw, fmt, ignore_slot=ignore_slot, hash_mod=hash_mod)
-    got = parse_ps_text_device(_dev(raw), fmt, hash_mod, ignore_slot=ignore_slot)
-    torch.cuda.synchronize()
-    assert got.rows == ref.rows and got.nnz == ref.nnz
-    assert got.bad_lines == ref.info["bad_lines"]
-    assert np.array_equal(got.labels.cpu().numpy().view(np.uint32),
-                          np.asarray(ref.labels, np.float32).view(np.uint32))
-    assert np.array_equal(got.row_ptr.cpu().numpy(), np.asarray(ref.row_ptr, np.int64))
-    assert np.array_equal(got.keys.cpu().numpy().view(np.uint64),
-                          np.asarray(ref.keys).view(np.uint64))
-    assert (got.vals is None) == (ref.vals is None)
-    if ref.vals is not None:
-        assert np.array_equal(got.vals.cpu().numpy().view(np.uint32),
-                              np.asarray(ref.vals, np.float32).view(np.uint32))
-    if ignore_slot:
-        assert got.slots is None
-    else:
-        assert got.slots.dtype == torch.int32
-        assert np.array_equal(got.slots.cpu().numpy(), np.asarray(ref.slots, np.int32))
-    w = np.diff(np.asarray(ref.row_ptr))
-    assert got.width == (int(w[0]) if w.size and w[0] > 0 and (w == w[0]).all() else 0)
-    if clean:
-        assert got.deferred is False and ref.info["bad_lines"] == 0
-    assert int(got.out.hdr.cpu()[7]) == 0  # capacity flag clear
-    return got
+_check = functools.partial(check_against_host, ignore_slot=False)
 
 
 # ------------------------------------------------------------------ corpora
@@ -301,12 +268,12 @@ def test_output_capacity_overflow_defers(corpora, fmt):
     raw = _join(corpora[fmt][:400])
     ref = data.parse_text(raw, fmt, ignore_slot=False)
     out = TextParseBuffers(100, 50, DEV)  # too small for 400 rows
-    got = parse_ps_text_device(_dev(raw), fmt, 0, ignore_slot=False, out=out)
+    got = parse_text_device(_dev(raw), fmt, 0, ignore_slot=False, out=out)
     assert got.deferred and got.rows == ref.rows and got.nnz == ref.nnz
     assert np.array_equal(got.keys.cpu().numpy().view(np.uint64), ref.keys.view(np.uint64))
     assert np.array_equal(got.slots.cpu().numpy(), ref.slots)
     # the sticky flag was cleared: the grown buffers parse on the device again
-    again = parse_ps_text_device(_dev(raw), fmt, 0, ignore_slot=False, out=out)
+    again = parse_text_device(_dev(raw), fmt, 0, ignore_slot=False, out=out)
     assert again.deferred is False and again.rows == ref.rows
     assert np.array_equal(again.slots.cpu().numpy(), ref.slots)
 
@@ -317,8 +284,8 @@ def test_base_offsets_behind_carried_rows(corpora, fmt):
     a, b = _join(rows[:300]), _join(rows[300:700], last_eol=False)
     ref = data.parse_text(a + b, fmt, ignore_slot=False, hash_mod=65536)
     out = TextParseBuffers(1000, 40000, DEV)
-    p1 = parse_ps_text_device(_dev(a), fmt, 65536, ignore_slot=False, out=out)
-    p2 = parse_ps_text_device(_dev(b), fmt, 65536, ignore_slot=False, out=out, row0=p1.rows,
+    p1 = parse_text_device(_dev(a), fmt, 65536, ignore_slot=False, out=out)
+    p2 = parse_text_device(_dev(b), fmt, 65536, ignore_slot=False, out=out, row0=p1.rows,
                               nnz0=p1.nnz)
     assert not p1.deferred and not p2.deferred
     n_rows, nnz = p1.rows + p2.rows, p1.nnz + p2.nnz
@@ -336,23 +303,31 @@ def test_base_offsets_behind_carried_rows(corpora, fmt):
 
     same()
     # a deferred second chunk lands behind the carried rows as well
-    p3 = parse_ps_text_device(_dev(b + b"\n; 9 3\n"), fmt, 65536, ignore_slot=False, out=out,
+    p3 = parse_text_device(_dev(b + b"\n; 9 3\n"), fmt, 65536, ignore_slot=False, out=out,
                               row0=p1.rows, nnz0=p1.nnz)
     assert p3.deferred and p3.bad_lines == 1 and p3.rows == p2.rows
     same()
 
 
 def test_supported_formats():
-    assert all(pstext.supported(f) for f in ("SPARSE_BINARY", "SPARSE", 2, 3))
-    assert not any(pstext.supported(f) for f in ("LIBSVM", "CRITEO", "ADFEA", "TERAFEA", "DENSE",
-                                                 "VW", 1, 4, 5, 6, 7, 8))
-    assert textparse.supported("LIBSVM") and textparse.supported("CRITEO")
-    assert not any(textparse.supported(f)
-                   for f in ("ADFEA", "TERAFEA", "SPARSE", "DENSE", "SPARSE_BINARY"))
+    names = ("DENSE", "SPARSE", "SPARSE_BINARY", "ADFEA", "LIBSVM", "TERAFEA", "VW", "CRITEO")
+    for k, f in enumerate(names, 1):
+        on = f not in ("DENSE", "VW")
+        assert textparse.supported(f) == textparse.supported(k) == on
+        assert (textparse.traits(f) is not None) == on
+        if on:
+            t = textparse.traits(f)
+            assert t == textparse.traits(k) and t.id == k == data.TEXT_FORMATS[f]
+            assert t.valued == (f in ("LIBSVM", "SPARSE"))
+            assert t.slots == (f in ("SPARSE", "SPARSE_BINARY", "ADFEA", "TERAFEA"))
+        assert textparse.produces_slots(f) == textparse.produces_slots(k) == \
+            (f in ("SPARSE", "SPARSE_BINARY", "ADFEA", "TERAFEA"))
     with pytest.raises(ValueError):
-        parse_ps_text_device(_dev(b"1 2:3\n"), "LIBSVM")
+        parse_text_device(_dev(b"1 2:3\n"), "LIBSVM", ignore_slot=False)
     with pytest.raises(ValueError):
-        textparse.parse_text_device(_dev(b"1; 2 3\n"), "SPARSE_BINARY")
+        parse_text_device(_dev(b"1\t2\t3\n"), "CRITEO", ignore_slot=False)
+    with pytest.raises(KeyError):
+        parse_text_device(_dev(b"1; 2 3\n"), "NOPE")
 
 
 # ------------------------------------------------------------------ feeder

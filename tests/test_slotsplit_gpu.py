@@ -160,7 +160,7 @@ def _files(tmp_path, fmt, rows=(1500, 1500)):
 
 @pytest.mark.parametrize("fmt", FMTS)
 def test_split_behind_carried_rows(tmp_path, fmt):
-    from parameter_server_amd.ops.pstext import parse_ps_text_device
+    from parameter_server_amd.ops.textparse import parse_text_device
     from parameter_server_amd.ops.textparse import TextParseBuffers
 
     raw = open(_files(tmp_path, fmt, (700,))[0], "rb").read()
@@ -168,8 +168,8 @@ def test_split_behind_carried_rows(tmp_path, fmt):
     a, b = raw[:cut], raw[cut:]
     dev = lambda x: torch.frombuffer(bytearray(x), dtype=torch.uint8).to(DEV)  # noqa: E731
     out = TextParseBuffers(1000, 40000, DEV)
-    p1 = parse_ps_text_device(dev(a), fmt, ignore_slot=False, out=out)
-    p2 = parse_ps_text_device(dev(b), fmt, ignore_slot=False, out=out, row0=p1.rows, nnz0=p1.nnz)
+    p1 = parse_text_device(dev(a), fmt, ignore_slot=False, out=out)
+    p2 = parse_text_device(dev(b), fmt, ignore_slot=False, out=out, row0=p1.rows, nnz0=p1.nnz)
     assert not p1.deferred and not p2.deferred and p1.nnz > 0 and int(p2.row_ptr[0]) == p1.nnz
     for p, text in ((p1, a), (p2, b)):
         ref = SlotData.from_batch(data.parse_text(text, fmt, ignore_slot=False)).groups

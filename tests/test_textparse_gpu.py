@@ -3,6 +3,7 @@ same bytes: labels, row offsets and keys bitwise, values bitwise or None by the 
 binary rule, bad-line and row counts -- on clean corpora (which must not be deferred to
 the host), at every boundary of the work decomposition, on malformed and random bytes,
 behind carried rows, through the DeviceFeeder and through the file-fed app."""
+import functools
 import os
 import random
 
@@ -14,39 +15,13 @@ from parameter_server_amd import data
 from parameter_server_amd.ops.native import core
 from parameter_server_amd.ops.textparse import (TextParseBuffers, parse_text_device,
                                                 segments_valued, supported)
+from parameter_server_amd.ops.textparse import traits as textparse_traits
+from textparse_cases import _dev, check_against_host
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 SPAN = 16384  # bytes of text per workgroup (textparse.hip)
-
-
-def _dev(raw: bytes) -> torch.Tensor:
-    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(DEV) if raw else \
-        torch.empty(0, dtype=torch.uint8, device=DEV)
-
-
-def _check(raw: bytes, fmt: str, hash_mod: int = 0, *, clean: bool = True):
-    """Device result == host result on ``raw``; returns the device result."""
-    ref = data.parse_text(raw, fmt, ignore_slot=True, hash_mod=hash_mod)
-    got = parse_text_device(_dev(raw), fmt, hash_mod)
-    torch.cuda.synchronize()
-    assert got.rows == ref.rows and got.nnz == ref.nnz
-    assert got.bad_lines == ref.info["bad_lines"]
-    assert np.array_equal(got.labels.cpu().numpy().view(np.uint32),
-                          np.asarray(ref.labels, np.float32).view(np.uint32))
-    assert np.array_equal(got.row_ptr.cpu().numpy(), np.asarray(ref.row_ptr, np.int64))
-    assert np.array_equal(got.keys.cpu().numpy().view(np.uint64),
-                          np.asarray(ref.keys).view(np.uint64))
-    assert (got.vals is None) == (ref.vals is None)
-    if ref.vals is not None:
-        assert np.array_equal(got.vals.cpu().numpy().view(np.uint32),
-                              np.asarray(ref.vals, np.float32).view(np.uint32))
-    w = np.diff(np.asarray(ref.row_ptr))
-    assert got.width == (int(w[0]) if w.size and w[0] > 0 and (w == w[0]).all() else 0)
-    if clean:
-        assert got.deferred is False and ref.info["bad_lines"] == 0
-    assert int(got.out.hdr.cpu()[7]) == 0  # capacity flag clear
-    return got
+_check = functools.partial(check_against_host, ignore_slot=True)
 
 
 # ------------------------------------------------------------------ corpora
@@ -256,11 +231,63 @@ def test_base_offsets_behind_carried_rows(libsvm_rows):
     assert np.array_equal(out.keys[:nnz].cpu().numpy().view(np.uint64), ref.keys.view(np.uint64))
 
 
+# ------------------------------------------------------------------ the one entry
+# three clean lines per format, smallest work space first: every call has to regrow what the
+# format before it left behind
+SIX = [("ADFEA", b"99 1 1 10:1 20:2\n7 1 0 30:1\n8 1 -3 5:6 4:2 3:1\n"),
+       ("TERAFEA", b"1 55 | 18014398509481985 5\n0 56 | 7\n-2 57 | 36028797018963970 8 9\n"),
+       ("LIBSVM", b"1 2:0.5 7:1\n-1 3:2\n0 4:1 9:3 11:-2e-3\n"),
+       ("CRITEO", b"1\t5\t7\n0\t3\n1\t\t9\t\t12\n"),
+       ("SPARSE_BINARY", b"1; 3 5 6; 7 9\n0; 2 4\n-1; 4096 1; 3 2 8\n"),
+       ("SPARSE", b"1; 3 5:0.5 6:1; 7 9:-2e-3\n0; 2 4:1\n-1; 1 8:3 9:0.25\n")]
+# one line shape per kernel family with 12-digit keys (~2.5 spans of them below)
+LONG = {"ADFEA": "{r} 1 1 {a}:3 {b}:7 {c}:3\n", "LIBSVM": "1 {a}:0.5 {b}:1 {c}:-2.25\n",
+        "SPARSE_BINARY": "1; 3 {a} {b}; 7 {c}\n"}
+
+
+def _straddling(fmt: str) -> bytes:
+    """40 KiB of clean ``fmt`` lines in which one key lies across byte 16384, the end of the
+    first span: the first line's key lengths shift everything behind it."""
+    rng = random.Random(7)
+    keys = sorted(rng.randrange(10 ** 11, 10 ** 12) for _ in range(3 * 1200))
+    body = "".join(LONG[fmt].format(r=r, a=keys[3 * r], b=keys[3 * r + 1], c=keys[3 * r + 2])
+                   for r in range(1200))
+    for d in range(2, 24):
+        first = LONG[fmt].format(r=0, a="1" * (d // 2), b="2" * (d - d // 2), c=10 ** 12)
+        raw = (first + body).encode()
+        raw = raw[:raw.rindex(b"\n", 0, 40 * 1024) + 1]
+        if raw[SPAN - 3:SPAN + 3].isdigit():
+            return raw
+    raise AssertionError("no key across the span edge")
+
+
+def test_six_formats_share_one_set_of_buffers():
+    from parameter_server_amd.ops.native import hipops
+
+    out = TextParseBuffers(1 << 15, 1 << 15, DEV)
+    family = None
+    for fmt, raw in SIX:
+        t = textparse_traits(fmt)
+        need = hipops().textparse_work_words(len(raw), t.id)
+        if t.family != family:  # (the first call of a family has to regrow the work space)
+            assert out.work is None or out.work.numel() < need
+        family = t.family
+        got = check_against_host(raw, fmt, 1000, ignore_slot=not t.slots, out=out)
+        assert got.rows == 3 and got.out is out and out.work.numel() >= need
+    for fmt in LONG:  # ~2.5 spans, one format per family: a token read across the span edge
+        raw = _straddling(fmt)
+        assert 2 * SPAN < len(raw) <= 40 * 1024
+        got = check_against_host(raw, fmt, 0, ignore_slot=not textparse_traits(fmt).slots, out=out)
+        assert got.rows > 700 and got.out is out
+
+
 def test_supported_formats_and_cpu_path():
-    assert supported("LIBSVM") and supported("CRITEO")
-    assert not any(supported(f) for f in ("ADFEA", "TERAFEA", "SPARSE", "DENSE", "SPARSE_BINARY"))
-    with pytest.raises(ValueError):
-        parse_text_device(_dev(b"1 2 | 3\n"), "TERAFEA")
+    assert all(supported(f) for f in ("LIBSVM", "CRITEO", "ADFEA", "TERAFEA", "SPARSE",
+                                      "SPARSE_BINARY"))
+    assert not supported("DENSE") and not supported("VW")
+    for fmt, line in (("DENSE", b"1 2 3\n"), ("VW", b"1 |a x:2\n")):
+        with pytest.raises(ValueError):
+            parse_text_device(_dev(line), fmt)
     got = parse_text_device(torch.frombuffer(bytearray(b"1 2 | 3\n"), dtype=torch.uint8), "TERAFEA")
     assert got.rows == 1 and not got.keys.is_cuda
     v = torch.tensor([1, 1, 2, 1, 1, 1, 0.5], device=DEV)
