@@ -16,8 +16,88 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 
+def csr_mode(args):
+    """1 GPU: the same Criteo-shaped minibatches through the fixed-width step and through the
+    ``row_ptr`` step (fm_csr), alternated window by window in this one process, then an
+    rcv1-shaped minibatch (about 75 valued features per row, 47,236 features), which only
+    the ``row_ptr`` step can take. Step times by a host clock around synchronised windows."""
+    from parameter_server_amd.models.fm import FMConfig, FMTrainer
+    from parameter_server_amd.ops.native import hipops
+    from parameter_server_amd.ops.synthetic import criteo_batch
+
+    dev = torch.device("cuda", 0)
+    B, N, S = args.minibatch, int(args.num_features), 39
+    tr = FMTrainer(FMConfig(localize=args.localize, num_features=N, embedding_dim=args.dim,
+                            minibatch=B, compact_rows=bool(args.compact_rows),
+                            table_capacity=args.table_slots, seed=0), device=dev)
+    crit = [criteo_batch(B, seed=77, row0=i * B, num_features=N, device=dev) for i in range(8)]
+    uniform = torch.arange(B + 1, device=dev) * S
+
+    g = torch.Generator().manual_seed(1)
+    rcv = []
+    for _ in range(4):
+        wid = torch.randint(50, 101, (B,), generator=g)
+        rp = torch.zeros(B + 1, dtype=torch.int64)
+        rp[1:] = wid.cumsum(0)
+        nnz = int(rp[-1])
+        # skewed feature ids: a few frequent terms, a long tail
+        k = (torch.rand(nnz, generator=g) ** 3 * 47236).long()
+        rcv.append((k.to(dev), torch.where(torch.rand(B, generator=g) < 0.5, 1.0, -1.0).to(dev),
+                    torch.rand(nnz, generator=g).to(dev), rp.to(dev)))
+    tr_rcv = FMTrainer(FMConfig(localize=args.localize, num_features=47236,
+                                embedding_dim=args.dim, minibatch=B, max_nnz=B * 100,
+                                compact_rows=bool(args.compact_rows), table_capacity=1 << 17,
+                                seed=0), device=dev)
+
+    def fixed(i):
+        tr.step(*crit[i % len(crit)])
+
+    def csr(i):
+        k, lab = crit[i % len(crit)]
+        tr.step(k, lab, row_ptr=uniform)
+
+    def rcv1(i):
+        k, lab, v, rp = rcv[i % len(rcv)]
+        tr_rcv.step(k, lab, vals=v, row_ptr=rp)
+
+    def window(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            fn(i)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps * 1e3
+
+    for fn in (fixed, csr, rcv1):
+        for i in range(args.warmup):
+            fn(i)
+    ms = {"fixed": [], "csr": [], "rcv1": []}
+    for r in range(args.repeats):
+        for name, fn in (("fixed", fixed), ("csr", csr), ("rcv1", rcv1)):
+            ms[name].append(window(fn))
+        print(f"window {r}: " + "  ".join(f"{n} {v[-1]:.3f} ms" for n, v in ms.items()),
+              flush=True)
+    med = {n: sorted(v)[len(v) // 2] for n, v in ms.items()}
+    H = hipops()
+    print(json.dumps({
+        "metric": "FM step time, fixed-width route vs row_ptr route (fm_csr), 1 GPU",
+        "unit": "ms/step (median of windows)", "steps_per_window": args.steps,
+        "windows": args.repeats, "minibatch": B, "embedding_dim": args.dim,
+        "criteo_fixed_ms": med["fixed"], "criteo_row_ptr_ms": med["csr"],
+        "rcv1_row_ptr_ms": med["rcv1"], "all_ms": ms,
+        "lanes": {"criteo": H.fm_csr_lanes(B * S, B),
+                  "rcv1": H.fm_csr_lanes(rcv[0][0].numel(), B)},
+        "rcv1_nnz": rcv[0][0].numel(),
+        "train": {"criteo": tr.progress(), "rcv1": tr_rcv.progress()},
+    }), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--csr", action="store_true",
+                    help="1 GPU: fixed-width step vs the row_ptr step on the same minibatches, "
+                         "alternated, and an rcv1-shaped valued minibatch")
+    ap.add_argument("--repeats", type=int, default=5, help="--csr: windows per route")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--localize", default="sort", choices=("sort", "part"))
     ap.add_argument("--warmup", type=int, default=5)
@@ -31,6 +111,8 @@ def main():
     ap.add_argument("--prefetch", type=int, default=1,
                     help="generate + localise minibatch t+1 on a side stream during step t")
     args = ap.parse_args()
+    if args.csr:
+        return csr_mode(args)
     from parameter_server_amd.models.fm import FMConfig, FMTrainer
     from parameter_server_amd.ops.synthetic import criteo_batch
     from parameter_server_amd.parallel.comm import init_from_env

@@ -63,6 +63,38 @@ FmArgs check_fm_sizes(const Tensor& local_col, const Tensor& labels, const Tenso
   return a;
 }
 
+// what the two fm_csr ops share: the row layout, the occurrences and the factor rows
+psamd::FmCsr check_fm_csr(const optional<Tensor>& row_ptr, int width, int64_t nnz,
+                          const Tensor* local_col, const optional<Tensor>& vals,
+                          const Tensor& rows, const optional<Tensor>& idx, int64_t B, int lanes) {
+  psamd::FmCsr a = {};
+  chk(rows, at::kBFloat16, "rows");
+  check(rows.dim() == 2, "rows [R, D]");
+  a.D = (int)rows.size(1);
+  check(a.D == 8 || a.D == 16 || a.D == 32, "fm_csr: D in {8, 16, 32}");
+  check(lanes == 0 || lanes == 16 || lanes == 32 || lanes == 64,
+        "lanes per row: 0 (auto), 16, 32 or 64");
+  check(B >= 0 && B < (int64_t(1) << 31) && nnz >= 0 && nnz < (int64_t(1) << 31),
+        "fm_csr: 0 <= B, nnz < 2^31");
+  a.row_ptr = optr<int64_t>(row_ptr, at::kLong, "row_ptr");
+  if (a.row_ptr) check(row_ptr->numel() >= B + 1, "row_ptr too small");
+  else check(width > 0 && B <= nnz / width, "fixed width layout too small");
+  a.width = width;
+  a.nnz = nnz;
+  a.B = B;
+  if (local_col) {
+    check(local_col->numel() >= nnz, "local_col too small");
+    a.local_col = ptr<int32_t>(*local_col);
+  }
+  a.vals = optr<float>(vals, at::kFloat, "vals");
+  if (a.vals) check(vals->numel() >= nnz, "vals too small");
+  a.rows = rows.data_ptr();
+  a.rows_cap = rows.size(0);
+  a.idx = optr<int64_t>(idx, at::kLong, "idx");
+  a.idx_cap = a.idx ? idx->numel() : 0;
+  return a;
+}
+
 }  // namespace
 
 void psamd_bind::register_linear(py::module_& m) {
@@ -240,6 +272,56 @@ void psamd_bind::register_linear(py::module_& m) {
                       ptr<float>(labels), ptr<float>(coef), dX0.data_ptr(), ptr<double>(metrics),
                       a.h, nbins, acc_stripes_of(metrics), cur_stream());
   });
+  // CSR rows of any width (fm.hip fm_csr): row_ptr [B + 1], or a fixed width when it is
+  // None. lanes: lanes per row, 0 = from nnz / B (fm_csr_lanes), else 16, 32 or 64.
+  m.def("fm_csr", [](optional<Tensor> row_ptr, int width, Tensor local_col, int64_t nnz,
+                     optional<Tensor> vals, Tensor rows, optional<Tensor> idx, Tensor w_local,
+                     Tensor labels, int64_t B, Tensor coef, Tensor dX0, Tensor row_of,
+                     Tensor metrics, optional<Tensor> hist, int nbins, int lanes) {
+    check_fm(dX0, local_col, w_local, labels, coef, metrics);
+    chk(row_of, at::kInt, "row_of");
+    psamd::FmCsr a = check_fm_csr(row_ptr, width, nnz, &local_col, vals, rows, idx, B, lanes);
+    a.w_local = ptr<float>(w_local);
+    a.w_cap = w_local.numel();
+    check(labels.numel() >= B && coef.numel() >= B, "labels/coef too small");
+    check(dX0.numel() >= a.nnz * a.D && row_of.numel() >= a.nnz, "dX0/row_of too small");
+    check(metrics.numel() >= 3, "metrics[3]");
+    a.hist = optr<uint32_t>(hist, at::kInt, "hist");
+    if (a.hist) check(nbins > 0 && hist->numel() >= 2 * nbins, "hist too small");
+    a.labels = ptr<float>(labels);
+    a.coef = ptr<float>(coef);
+    a.dX0 = dX0.data_ptr();
+    a.row_of = ptr<int32_t>(row_of);
+    a.metrics = ptr<double>(metrics);
+    a.nbins = nbins;
+    a.acc_stripes = acc_stripes_of(metrics);
+    psamd::fm_csr(a, lanes, cur_stream());
+  }, py::arg("row_ptr"), py::arg("width"), py::arg("local_col"), py::arg("nnz"), py::arg("vals"),
+     py::arg("rows"), py::arg("idx"), py::arg("w_local"), py::arg("labels"), py::arg("B"),
+     py::arg("coef"),
+     py::arg("dX0"), py::arg("row_of"), py::arg("metrics"), py::arg("hist"), py::arg("nbins"),
+     py::arg("lanes") = 0);
+  // the forward-only form: margins [B] and nothing else. local_col None: column =
+  // position (idx and w_local per occurrence, as table.resolve returns them), nnz entries
+  m.def("fm_csr_margins", [](optional<Tensor> row_ptr, int width, optional<Tensor> local_col,
+                             int64_t nnz, optional<Tensor> vals, Tensor rows,
+                             optional<Tensor> idx, Tensor w_local, int64_t B, Tensor margins,
+                             int lanes) {
+    chk(w_local, at::kFloat, "w_local");
+    chk(margins, at::kFloat, "margins");
+    const bool lc = local_col.has_value() && local_col->defined();
+    if (lc) chk(*local_col, at::kInt, "local_col");
+    psamd::FmCsr a = check_fm_csr(row_ptr, width, nnz, lc ? &*local_col : nullptr, vals, rows,
+                                  idx, B, lanes);
+    check(margins.numel() >= B, "margins too small");
+    a.w_local = ptr<float>(w_local);
+    a.w_cap = w_local.numel();
+    a.margins = ptr<float>(margins);
+    psamd::fm_csr_margins(a, lanes, cur_stream());
+  }, py::arg("row_ptr"), py::arg("width"), py::arg("local_col"), py::arg("nnz"), py::arg("vals"),
+     py::arg("rows"), py::arg("idx"), py::arg("w_local"), py::arg("B"), py::arg("margins"),
+     py::arg("lanes") = 0);
+  m.def("fm_csr_lanes", &psamd::fm_csr_lanes);
   m.def("fm_l2", [](Tensor dE, Tensor rows, optional<Tensor> idx, optional<Tensor> n_dev,
                     int64_t u_cap, double lambda) {
     chk(dE, at::kFloat, "dE");

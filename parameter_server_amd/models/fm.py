@@ -18,6 +18,10 @@ Per step: localise -> pull rows + w -> expand X0 [B*S, k] -> ``fm_fwd_bwd`` (one
 wavefront per example: s_f, q_f, margin, loss / accuracy / AUC, dX0 = p (x s - x^2
 v)) -> per-key reduction of dX0 (CSC order) + L2 -> AdaGrad rows; wide gradient by
 the sparse-LR segmented reduction -> AdaGrad (proximal L2) on w.
+
+``step(..., row_ptr=)`` takes CSR minibatches (rows of any width, optional values): the
+same step with ``fm_csr`` (fm.hip: a group of 16 / 32 / 64 lanes per row) in place of
+``fm_fwd_bwd``; ``predict`` on a GPU trainer runs its forward-only form.
 """
 from __future__ import annotations
 
@@ -65,6 +69,9 @@ class FMConfig:
     # per-bucket LDS dedup, run order inside a segment set by atomics; B = 65536: 0.563
     # vs 0.587 ms / step, profiles/r2_asp_tail.log)
     localize: str = "sort"
+    # most keys of one minibatch; 0: minibatch * slots. Variable-width minibatches
+    # (step(row_ptr=...)) may hold any number of keys up to this
+    max_nnz: int = 0
     seed: int = 0
 
 
@@ -86,7 +93,7 @@ class FMTrainer(EmbeddingPS):
         cap = max(1024, min(cap, 1 << max(10, (cfg.max_table_bytes // per_slot).bit_length() - 1)))
         self.shard = E.EmbeddingShard(cap, D, dev, init_scale=cfg.emb_init_scale,
                                       seed=cfg.seed * 7919 + 17)
-        self.max_nnz = B * S
+        self.max_nnz = cfg.max_nnz or B * S
         self.localizer = Localizer(self.max_nnz, self.bits, dev, mode=cfg.localize)
         self.coef = torch.empty(B, dtype=torch.float32, device=dev)
         self.metrics = new_accum(dev)
@@ -99,15 +106,20 @@ class FMTrainer(EmbeddingPS):
             self.dX0 = torch.empty(self.max_nnz, D, dtype=torch.bfloat16, device=dev)
             self.dE = torch.empty(self.max_nnz, D, dtype=torch.float32, device=dev)
             self.rows_u = torch.empty(self.max_nnz, D, dtype=torch.bfloat16, device=dev)
+            self.row_of = None  # [max_nnz] int32, on the first CSR step
         self.step_count = 0
         self.examples = 0
         self.t0 = time.time()
 
     # ------------------------------------------------------------------ step
     def step(self, keys: torch.Tensor, labels: torch.Tensor, vals: torch.Tensor | None = None,
-             loc=None):
+             loc=None, row_ptr: torch.Tensor | None = None):
         """One minibatch: ``keys`` [B*S] raw feature ids (row-major, S per example),
-        ``labels`` [B] in {-1, +1} (or {0, 1}), optional feature values ``vals``."""
+        ``labels`` [B] in {-1, +1} (or {0, 1}), optional feature values ``vals``. With
+        ``row_ptr`` [B + 1] (int64) the rows have any width (CSR, as the text parsers and
+        the device feeder produce them): row b holds keys[row_ptr[b]:row_ptr[b + 1]]."""
+        if row_ptr is not None:
+            return self._step_csr(keys, labels, vals, loc, row_ptr)
         cfg = self.cfg
         S, D = cfg.slots, cfg.embedding_dim
         B = labels.numel()
@@ -185,23 +197,140 @@ class FMTrainer(EmbeddingPS):
             self.hist.dtype)
         return dX.reshape(B * S, D).to(torch.bfloat16)
 
+    # ------------------------------------------------------------------ CSR rows
+    def _check_csr(self, nnz: int, B: int, row_ptr: torch.Tensor, vals) -> None:
+        """Everything a CSR minibatch can get wrong, before anything is launched."""
+        D = self.cfg.embedding_dim
+        if row_ptr.numel() != B + 1:
+            raise ValueError(f"row_ptr has {row_ptr.numel()} entries for {B} rows, not {B + 1}")
+        if row_ptr.dtype != torch.int64:
+            raise ValueError("row_ptr must be int64")
+        if vals is not None and vals.numel() != nnz:
+            raise ValueError(f"expected {nnz} values, got {vals.numel()}")
+        if self.gpu and D not in (8, 16, 32):
+            raise ValueError(f"variable-width rows on the GPU need embedding_dim in (8, 16, 32), "
+                             f"not {D}")
+
+    def _step_csr(self, keys, labels, vals, loc, row_ptr):
+        """step() on variable-width rows: the fixed-width step with ``fm_csr`` (lane groups
+        per row, fm.hip) as its forward / backward, and the row id of every occurrence, which
+        the kernel writes, for the wide gradient. Nothing here depends on the world size."""
+        cfg = self.cfg
+        D = cfg.embedding_dim
+        B, nnz = labels.numel(), keys.numel()
+        self._check_csr(nnz, B, row_ptr, vals)
+        if nnz > self.max_nnz:
+            raise ValueError(f"{nnz} keys in a minibatch, max_nnz is {self.max_nnz}")
+        if B > self.coef.numel():
+            raise ValueError(f"{B} rows in a minibatch, cfg.minibatch is {self.coef.numel()}")
+        loc = self.localizer(keys) if loc is None else loc
+        if self.G == 1:
+            if self.gpu:
+                slot, w_wide = self.shard.resolve(loc.uniq, loc.n_uniq, self.slot_buf, self.w_buf)
+            else:
+                slot, w_wide = self.shard.resolve(loc.uniq[:loc.num_unique()])
+            rows_src, rows_idx = self.shard.rows, slot
+            if self.gpu and cfg.compact_rows:
+                hipops().emb_gather_rows(slot, self.shard.rows, self.rows_u, loc.n_uniq)
+                rows_src, rows_idx = self.rows_u, None
+            push = ("local", slot)
+        else:
+            rows_u, w_wide, push = self._pull(loc)
+            rows_src, rows_idx = rows_u, None
+        if self.gpu:
+            if self.row_of is None:
+                self.row_of = torch.empty(self.max_nnz, dtype=torch.int32, device=self.device)
+            dX0, row_of = self.dX0[:nnz], self.row_of[:nnz]
+            hipops().fm_csr(row_ptr, 0, loc.local_col, nnz, vals, rows_src, rows_idx, w_wide,
+                            labels, B, self.coef, dX0, row_of, self.metrics, self.hist, AUC_BINS)
+            dE = E.grad_reduce(loc, dX0, D, nnz, out=self.dE)
+            l2_cap = nnz if rows_idx is not None else min(nnz, rows_src.shape[0])
+            hipops().fm_l2(dE, rows_src, rows_idx, loc.n_uniq, l2_cap, cfg.lambda_v)
+        else:
+            X0 = E.expand(loc.local_col, nnz, rows_src, idx=rows_idx)
+            row_of = torch.repeat_interleave(torch.arange(B), row_ptr[1:] - row_ptr[:-1])
+            dX0 = self._fwd_bwd_torch_csr(X0, vals, row_of, loc.local_col, w_wide, labels)
+            U = loc.num_unique()
+            dE = E.grad_reduce(loc, dX0, D, U)
+            v = (rows_src[rows_idx[:U]] if rows_idx is not None else rows_src[:U]).float()
+            dE += cfg.lambda_v * v
+        g_wide, _ = linear_backward(loc, self.coef[:B], B=B, rows=row_of, vals=vals)
+        self._push(loc, push, dE, g_wide)
+        auc_from_hist(self.hist, self.metrics, self.step_dev)
+        self.step_count += 1
+        self.examples += B
+
+    def _fwd_bwd_torch_csr(self, X0, vals, row_of, local_col, w_wide, labels, dtype=torch.float32):
+        """_fwd_bwd_torch on CSR rows: ``row_of`` [nnz] is the row of every occurrence and
+        the per-row sums are segment sums (index_add_ by row id). The CPU route, and in
+        ``dtype=torch.float64`` the reference the fm_csr kernels are tested against."""
+        nnz, B = row_of.numel(), labels.numel()
+        D = X0.shape[1]
+        r = row_of.long()
+        x = (vals.to(dtype) if vals is not None else torch.ones(nnz, dtype=dtype))[:, None]
+        V = X0[:nnz].to(dtype)
+        xv = x * V
+        s = torch.zeros(B, D, dtype=dtype).index_add_(0, r, xv)
+        q = torch.zeros(B, dtype=dtype).index_add_(0, r, (xv * xv).sum(1))
+        lin = torch.zeros(B, dtype=dtype).index_add_(
+            0, r, w_wide.to(dtype)[local_col[:nnz].long()] * x[:, 0])
+        m = lin + 0.5 * ((s * s).sum(1) - q)
+        y = torch.where(labels > 0, 1.0, -1.0).to(dtype)
+        ym = y * m
+        c = -y * torch.sigmoid(-ym)
+        self.coef[:B] = c
+        dX = c[r, None] * (x * s[r] - x * x * V)
+        self.metrics[0] += torch.nn.functional.softplus(-ym).double().sum()
+        self.metrics[1] += ((y > 0) == (m > 0)).double().sum()
+        self.metrics[2] += B
+        nb = AUC_BINS
+        pb = torch.clamp((torch.sigmoid(m) * nb).long(), 0, nb - 1)
+        self.hist += torch.bincount(pb + torch.where(y > 0, nb, 0), minlength=2 * nb).to(
+            self.hist.dtype)
+        return dX.to(torch.bfloat16)
+
     # ------------------------------------------------------------------ eval
-    def predict(self, keys: torch.Tensor, B: int) -> torch.Tensor:
-        """Margins of B examples (no update; unseen keys contribute 0). G == 1."""
+    def predict(self, keys: torch.Tensor, B: int, vals: torch.Tensor | None = None,
+                row_ptr: torch.Tensor | None = None) -> torch.Tensor:
+        """Margins of B examples (no update; unseen keys contribute 0). G == 1. Rows of
+        ``cfg.slots`` keys, or of any width with ``row_ptr`` [B + 1]; optional ``vals``.
+        A GPU trainer scores with the forward-only ``fm_csr`` kernel (fm.hip)."""
         if self.G != 1:
             raise NotImplementedError("predict() reads the local shard (G == 1)")
         from ..ops.keymix import mix
 
         S, D = self.cfg.slots, self.cfg.embedding_dim
+        nnz = keys.numel()
+        if row_ptr is not None:
+            self._check_csr(nnz, B, row_ptr, vals)
+        elif nnz != B * S:
+            raise ValueError(f"expected {B * S} keys, got {nnz}")
         mk = mix(keys.to(self.device), self.bits)
         slot, w = self.shard.table.resolve(mk, insert=False)
         ok = slot >= 0
-        V = torch.zeros(mk.numel(), D, device=self.device)
-        V[ok] = self.shard.rows[slot[ok]].float()
         w = torch.where(ok, w, torch.zeros_like(w))
-        V = V.reshape(B, S, D)
-        s = V.sum(1)
-        return w.reshape(B, S).sum(1) + 0.5 * (s * s - (V * V).sum(1)).sum(1)
+        if self.gpu:
+            if D not in (8, 16, 32):
+                raise ValueError(f"predict() on the GPU needs embedding_dim in (8, 16, 32), "
+                                 f"not {D}")
+            # slot and w are per occurrence: no local columns, the rows through slot
+            margins = torch.empty(B, dtype=torch.float32, device=self.device)
+            hipops().fm_csr_margins(row_ptr, S, None, nnz, vals, self.shard.rows, slot, w, B,
+                                    margins)
+            return margins
+        V = torch.zeros(nnz, D, device=self.device)
+        V[ok] = self.shard.rows[slot[ok]].float()
+        if vals is not None:
+            V = V * vals.float()[:, None]
+            w = w * vals.float()
+        if row_ptr is None:
+            V = V.reshape(B, S, D)
+            s = V.sum(1)
+            return w.reshape(B, S).sum(1) + 0.5 * (s * s - (V * V).sum(1)).sum(1)
+        r = torch.repeat_interleave(torch.arange(B), row_ptr[1:] - row_ptr[:-1])
+        s = torch.zeros(B, D).index_add_(0, r, V)
+        q = torch.zeros(B).index_add_(0, r, (V * V).sum(1))
+        return torch.zeros(B).index_add_(0, r, w) + 0.5 * ((s * s).sum(1) - q)
 
     def progress(self, reset: bool = True) -> dict:
         self._xe_check()

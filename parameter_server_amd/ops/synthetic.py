@@ -76,6 +76,20 @@ def criteo_batch(B: int, *, seed: int, row0: int, num_features: int, alpha: floa
     return keys, labels
 
 
+def drop_slots(keys: torch.Tensor, B: int, *, keep: float, seed: int):
+    """Rows of a fixed-width minibatch with slots missing, as CSR: every key of ``keys``
+    [B * S] stays with probability ``keep``. Returns (keys [nnz], row_ptr int64 [B + 1],
+    vals float32 [nnz] in [0.5, 1.5)), on the device of ``keys``. (Host random numbers:
+    the same rows on a CPU and a GPU trainer.)"""
+    g = torch.Generator().manual_seed(seed)
+    mask = torch.rand(keys.numel(), generator=g) < keep
+    row_ptr = torch.zeros(B + 1, dtype=torch.int64)
+    row_ptr[1:] = mask.reshape(B, -1).sum(1).cumsum(0)
+    vals = torch.rand(int(row_ptr[-1]), generator=g) + 0.5
+    dev = keys.device
+    return keys[mask.to(dev)].contiguous(), row_ptr.to(dev), vals.to(dev)
+
+
 # ----------------------------------------------------------------------------- CPU path
 def _mix32(x):
     """gen_mix32 of linear.hip on numpy uint32 arrays (wrapping arithmetic)."""
