@@ -16,6 +16,104 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 
+def rcv1_batches(B, n, dev):
+    """n rcv1-shaped minibatches (keys, labels, vals, row_ptr): 50..100 valued features per
+    row out of 47,236, skewed ids (a few frequent terms, a long tail)."""
+    g = torch.Generator().manual_seed(1)
+    out = []
+    for _ in range(n):
+        wid = torch.randint(50, 101, (B,), generator=g)
+        rp = torch.zeros(B + 1, dtype=torch.int64)
+        rp[1:] = wid.cumsum(0)
+        nnz = int(rp[-1])
+        k = (torch.rand(nnz, generator=g) ** 3 * 47236).long()
+        out.append((k.to(dev), torch.where(torch.rand(B, generator=g) < 0.5, 1.0, -1.0).to(dev),
+                    torch.rand(nnz, generator=g).to(dev), rp.to(dev)))
+    return out
+
+
+def score_mode(args):
+    """1 GPU: scoring held-out minibatches with the fused kernel (``FMTrainer.scorer()``:
+    fm_predict.hip, margins only and labels + accumulator) and with the composed route
+    (``FMTrainer.predict``: mix, resolve, where, fm_csr forward), alternated window by window
+    in this one process, on a table filled by a few training steps. Criteo-shaped B x 39 for
+    D in {16, 32} (both routes) and {64, 128} (the scorer alone: ``predict`` refuses them on
+    a GPU), then an rcv1-shaped valued CSR minibatch at D = 16. Times by a host clock around
+    synchronised windows of ``--steps`` (at least 200) minibatches."""
+    from parameter_server_amd.models.fm import FMConfig, FMTrainer
+    from parameter_server_amd.ops.native import hipops
+    from parameter_server_amd.ops.synthetic import criteo_batch
+
+    dev = torch.device("cuda", 0)
+    B, N, S, n = args.minibatch, int(args.num_features), 39, max(args.steps, 200)
+
+    def measure(tag, tr, train, held, lanes):
+        """held: (keys, labels, the scorer's keywords, predict's keywords) per minibatch"""
+        for i in range(args.train_steps):
+            train(i)
+        sc = tr.scorer()
+        routes = {"fused_margins": lambda b: sc.predict(b[0], **b[2]),
+                  "fused_labels_acc": lambda b: sc.score(b[0], b[1], margins=False, **b[2])}
+        if tr.cfg.embedding_dim in (8, 16, 32):
+            routes["composed_predict"] = lambda b: tr.predict(b[0], B, **b[3])
+            a, c = routes["fused_margins"](held[0]), routes["composed_predict"](held[0])
+            print(f"{tag}: max |fused - composed| margin = {float((a - c).abs().max()):.3g}, "
+                  f"max |margin| = {float(c.abs().max()):.3g}", flush=True)
+        ms = {name: [] for name in routes}
+        for fn in routes.values():
+            for i in range(args.warmup):
+                fn(held[i % len(held)])
+        for r in range(args.repeats):
+            for name, fn in routes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(n):
+                    fn(held[i % len(held)])
+                torch.cuda.synchronize()
+                ms[name].append((time.perf_counter() - t0) / n * 1e3)
+            print(f"{tag} window {r}: " + "  ".join(f"{k} {v[-1]:.4f} ms" for k, v in ms.items()),
+                  flush=True)
+        occ, _ = tr.shard.table.census()
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        out = {"keys_in_table": occ, "table_slots": tr.shard.capacity, "lanes": lanes,
+               "eval": sc.result(), "ms": ms, "median_ms": med}
+        if "composed_predict" in med:
+            out["composed_over_fused_margins"] = med["composed_predict"] / med["fused_margins"]
+        return out
+
+    res = {}
+    H = hipops()
+    for D in (16, 32, 64, 128):
+        tr = FMTrainer(FMConfig(localize=args.localize, num_features=N, embedding_dim=D,
+                                minibatch=B, table_capacity=args.table_slots, seed=0), device=dev)
+        crit = [criteo_batch(B, seed=77, row0=i * B, num_features=N, device=dev)
+                for i in range(args.train_steps + 8)]
+        held = [(k, y, dict(width=S), {}) for k, y in crit[args.train_steps:]]
+        res[f"criteo_D{D}"] = measure(f"criteo D={D}", tr, lambda i: tr.step(*crit[i]), held,
+                                      H.fm_csr_lanes(B * S, B))
+        del tr, crit, held
+        torch.cuda.empty_cache()
+    rcv = rcv1_batches(B, 8, dev)
+    tr = FMTrainer(FMConfig(localize=args.localize, num_features=47236, embedding_dim=16,
+                            minibatch=B, max_nnz=B * 100, table_capacity=1 << 17, seed=0),
+                   device=dev)
+    held = [(k, y, dict(row_ptr=rp, vals=v), dict(row_ptr=rp, vals=v)) for k, y, v, rp in rcv[4:]]
+
+    def train_rcv(i):
+        k, y, v, rp = rcv[i % 4]
+        tr.step(k, y, vals=v, row_ptr=rp)
+
+    res["rcv1_D16"] = measure("rcv1 D=16", tr, train_rcv, held,
+                              H.fm_csr_lanes(rcv[4][0].numel(), B))
+    res["rcv1_D16"]["nnz"] = rcv[4][0].numel()
+    print(json.dumps({
+        "metric": "FM scoring time per minibatch, fused kernel (FMScorer) vs FMTrainer.predict, "
+                  "1 GPU", "unit": "ms/minibatch (median of windows)",
+        "minibatches_per_window": n, "windows": args.repeats, "minibatch": B,
+        "train_steps": args.train_steps, "lane_thresholds": "fm_csr_lanes, not swept", **res}),
+          flush=True)
+
+
 def csr_mode(args):
     """1 GPU: the same Criteo-shaped minibatches through the fixed-width step and through the
     ``row_ptr`` step (fm_csr), alternated window by window in this one process, then an
@@ -33,17 +131,7 @@ def csr_mode(args):
     crit = [criteo_batch(B, seed=77, row0=i * B, num_features=N, device=dev) for i in range(8)]
     uniform = torch.arange(B + 1, device=dev) * S
 
-    g = torch.Generator().manual_seed(1)
-    rcv = []
-    for _ in range(4):
-        wid = torch.randint(50, 101, (B,), generator=g)
-        rp = torch.zeros(B + 1, dtype=torch.int64)
-        rp[1:] = wid.cumsum(0)
-        nnz = int(rp[-1])
-        # skewed feature ids: a few frequent terms, a long tail
-        k = (torch.rand(nnz, generator=g) ** 3 * 47236).long()
-        rcv.append((k.to(dev), torch.where(torch.rand(B, generator=g) < 0.5, 1.0, -1.0).to(dev),
-                    torch.rand(nnz, generator=g).to(dev), rp.to(dev)))
+    rcv = rcv1_batches(B, 4, dev)
     tr_rcv = FMTrainer(FMConfig(localize=args.localize, num_features=47236,
                                 embedding_dim=args.dim, minibatch=B, max_nnz=B * 100,
                                 compact_rows=bool(args.compact_rows), table_capacity=1 << 17,
@@ -97,7 +185,12 @@ def main():
     ap.add_argument("--csr", action="store_true",
                     help="1 GPU: fixed-width step vs the row_ptr step on the same minibatches, "
                          "alternated, and an rcv1-shaped valued minibatch")
-    ap.add_argument("--repeats", type=int, default=5, help="--csr: windows per route")
+    ap.add_argument("--score", action="store_true",
+                    help="1 GPU: the fused scoring kernel (FMScorer) vs FMTrainer.predict on "
+                         "held-out minibatches, alternated; D in {16, 32, 64, 128} and rcv1")
+    ap.add_argument("--train-steps", type=int, default=20,
+                    help="--score: training steps that fill the table first")
+    ap.add_argument("--repeats", type=int, default=5, help="--csr / --score: windows per route")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--localize", default="sort", choices=("sort", "part"))
     ap.add_argument("--warmup", type=int, default=5)
@@ -113,6 +206,8 @@ def main():
     args = ap.parse_args()
     if args.csr:
         return csr_mode(args)
+    if args.score:
+        return score_mode(args)
     from parameter_server_amd.models.fm import FMConfig, FMTrainer
     from parameter_server_amd.ops.synthetic import criteo_batch
     from parameter_server_amd.parallel.comm import init_from_env

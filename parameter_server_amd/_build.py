@@ -33,6 +33,11 @@ BUILD = PKG.parent / "build" / "native"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 CXX = shutil.which("g++") or "c++"
+# Units built without the packed fp32 forms (v_pk_fma_f32 and its kin) as a target feature
+# of the whole unit, header functions included, so that everything still inlines (fm.hip
+# says the same per kernel, with a target attribute).
+NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+NO_PACKED_F32_UNITS = {"fm_predict.hip"}
 
 
 def _py_includes() -> list[str]:
@@ -81,7 +86,8 @@ def build_hipops(jobs: int = 8, verbose: bool = False) -> Path:
         obj = out_dir / (src.stem + ".o")
         objs.append(obj)
         if _stale(obj, src, headers):
-            jobs_list.append([HIPCC, *common, "-c", str(src), "-o", str(obj)])
+            extra = NO_PACKED_F32 if src.name in NO_PACKED_F32_UNITS else []
+            jobs_list.append([HIPCC, *common, *extra, "-c", str(src), "-o", str(obj)])
     tflags = [f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-DTORCH_EXTENSION_NAME=_hipops",
               "-DTORCH_API_INCLUDE_EXTENSION_H", "-DUSE_ROCM=1", "-D__HIP_PLATFORM_AMD__=1"]
     incs = sum((["-isystem", p] for p in inc + _py_includes()), [])

@@ -1,9 +1,10 @@
-// Bindings of the linear model (linear.hip), stored-model scoring (predict.hip), the
-// factorization machine (fm.hip) and the synthetic Criteo generator.
+// Bindings of the linear model (linear.hip), stored-model scoring (predict.hip,
+// fm_predict.hip), the factorization machine (fm.hip) and the synthetic Criteo generator.
 #include <memory>
 
 #include "bind_common.h"
 #include "fm.h"
+#include "fm_predict.h"
 #include "linear.h"
 #include "predict.h"
 
@@ -95,6 +96,46 @@ psamd::FmCsr check_fm_csr(const optional<Tensor>& row_ptr, int width, int64_t nn
   return a;
 }
 
+// what the two scoring ops (predict_rows, fm_predict_rows) share: the rows of raw keys and
+// the optional outputs. metrics / hist need labels.
+struct ScoreArgs {
+  int64_t nnz;
+  const int64_t* rp;
+  const float *v, *lb;
+  float* mg;
+  psamd::StripedAcc acc;
+  unsigned long long* hp;
+  int hist_stripes;
+};
+ScoreArgs check_score(const Tensor& keys, const optional<Tensor>& row_ptr, int width,
+                      const optional<Tensor>& vals, const optional<Tensor>& labels, int64_t B,
+                      int loss_type, const optional<Tensor>& margin,
+                      const optional<Tensor>& metrics, const optional<Tensor>& hist, int nbins,
+                      const std::string& op) {
+  ScoreArgs a;
+  chk(keys, at::kLong, "keys");
+  a.nnz = keys.numel();
+  check(B >= 0, op + ": B >= 0");
+  a.rp = optr<int64_t>(row_ptr, at::kLong, "row_ptr");
+  if (a.rp) check(row_ptr->numel() >= B + 1, "row_ptr too small");
+  else check(width > 0 && B <= a.nnz / width, "fixed width layout too small");
+  a.v = optr<float>(vals, at::kFloat, "vals");
+  if (a.v) check(vals->numel() >= a.nnz, "vals too small");
+  a.lb = optr<float>(labels, at::kFloat, "labels");
+  if (a.lb) check(labels->numel() >= B, "labels too small");
+  a.mg = optr<float>(margin, at::kFloat, "margin");
+  if (a.mg) check(margin->numel() >= B, "margin too small");
+  a.acc = striped_acc(metrics, "metrics");
+  if (a.acc.ptr) check(a.lb && metrics->numel() >= 3, "metrics needs labels and >= 3 slots");
+  a.hp = optr<unsigned long long>(hist, at::kLong, "hist");
+  if (a.hp) check(a.lb && nbins > 0 && nbins <= 8192 && hist->numel() >= 2 * nbins &&
+                      hist->numel() % (2 * nbins) == 0,
+                  "hist needs labels and int64 [stripes x 2 x nbins], nbins <= 8192");
+  a.hist_stripes = a.hp ? (int)(hist->numel() / (2 * nbins)) : 1;
+  check(loss_type >= 1 && loss_type <= 4, "loss type in [1, 4]");
+  return a;
+}
+
 }  // namespace
 
 void psamd_bind::register_linear(py::module_& m) {
@@ -136,32 +177,40 @@ void psamd_bind::register_linear(py::module_& m) {
                            optional<Tensor> margin, optional<Tensor> metrics,
                            optional<Tensor> hist, int nbins, int lanes) {
     const psamd::TableRef t = table_ref(slots, home_base, home_m);
-    chk(keys, at::kLong, "keys");
-    const int64_t nnz = keys.numel();
-    check(B >= 0, "predict_rows: B >= 0");
-    const int64_t* rp = optr<int64_t>(row_ptr, at::kLong, "row_ptr");
-    if (rp) check(row_ptr->numel() >= B + 1, "row_ptr too small");
-    else check(width > 0 && B <= nnz / width, "fixed width layout too small");
-    const float* v = optr<float>(vals, at::kFloat, "vals");
-    if (v) check(vals->numel() >= nnz, "vals too small");
-    const float* lb = optr<float>(labels, at::kFloat, "labels");
-    if (lb) check(labels->numel() >= B, "labels too small");
-    float* mg = optr<float>(margin, at::kFloat, "margin");
-    if (mg) check(margin->numel() >= B, "margin too small");
-    const psamd::StripedAcc acc = striped_acc(metrics, "metrics");
-    if (acc.ptr) check(lb && metrics->numel() >= 3, "metrics needs labels and >= 3 slots");
-    unsigned long long* hp = optr<unsigned long long>(hist, at::kLong, "hist");
-    if (hp) check(lb && nbins > 0 && nbins <= 8192 && hist->numel() >= 2 * nbins &&
-                      hist->numel() % (2 * nbins) == 0,
-                  "hist needs labels and int64 [stripes x 2 x nbins], nbins <= 8192");
+    const ScoreArgs a = check_score(keys, row_ptr, width, vals, labels, B, loss_type, margin,
+                                    metrics, hist, nbins, "predict_rows");
     check(lanes == 0 || lanes == 8 || lanes == 64, "lanes per row: 0 (auto), 8 or 64");
-    check(loss_type >= 1 && loss_type <= 4, "loss type in [1, 4]");
-    psamd::predict_rows(t, make_keymix(bits), ptr<uint64_t>(keys), nnz, rp, width, v, lb, B,
-                        loss_type, mg, acc, hp, nbins,
-                        hp ? (int)(hist->numel() / (2 * nbins)) : 1, lanes, cur_stream());
+    psamd::predict_rows(t, make_keymix(bits), ptr<uint64_t>(keys), a.nnz, a.rp, width, a.v, a.lb,
+                        B, loss_type, a.mg, a.acc, a.hp, nbins, a.hist_stripes, lanes,
+                        cur_stream());
   }, py::arg("slots"), py::arg("home_base"), py::arg("home_m"), py::arg("keys"), py::arg("bits"),
      py::arg("row_ptr"), py::arg("width"), py::arg("vals"), py::arg("labels"), py::arg("B"),
      py::arg("loss_type"), py::arg("margin"), py::arg("metrics"), py::arg("hist"),
+     py::arg("nbins"), py::arg("lanes") = 0);
+  // The same for a factorization machine (fm_predict.hip): rows [cap, D] bf16 are the factor
+  // rows at the slot index of every key (EmbeddingShard.rows), D a multiple of 8 up to 128.
+  // lanes: lanes per row, 0 = from nnz / B (fm_csr_lanes), else 16, 32 or 64.
+  m.def("fm_predict_rows", [](Tensor slots, uint64_t home_base, uint64_t home_m, Tensor rows,
+                              Tensor keys, int bits, optional<Tensor> row_ptr, int width,
+                              optional<Tensor> vals, optional<Tensor> labels, int64_t B,
+                              int loss_type, optional<Tensor> margin, optional<Tensor> metrics,
+                              optional<Tensor> hist, int nbins, int lanes) {
+    const psamd::TableRef t = table_ref(slots, home_base, home_m);
+    chk(rows, at::kBFloat16, "rows");
+    check(rows.dim() == 2 && rows.size(0) == t.cap, "rows must be [table capacity, D]");
+    const int64_t D = rows.size(1);
+    check(D > 0 && D % 8 == 0 && D <= 128, "fm_predict_rows: D a multiple of 8 up to 128");
+    check(t.cap <= (int64_t(1) << 31), "fm_predict_rows: at most 2^31 slots");
+    const ScoreArgs a = check_score(keys, row_ptr, width, vals, labels, B, loss_type, margin,
+                                    metrics, hist, nbins, "fm_predict_rows");
+    check(lanes == 0 || lanes == 16 || lanes == 32 || lanes == 64,
+          "lanes per row: 0 (auto), 16, 32 or 64");
+    psamd::fm_predict_rows(t, make_keymix(bits), rows.data_ptr(), (int)D, ptr<uint64_t>(keys),
+                           a.nnz, a.rp, width, a.v, a.lb, B, loss_type, a.mg, a.acc, a.hp, nbins,
+                           a.hist_stripes, lanes, cur_stream());
+  }, py::arg("slots"), py::arg("home_base"), py::arg("home_m"), py::arg("rows"), py::arg("keys"),
+     py::arg("bits"), py::arg("row_ptr"), py::arg("width"), py::arg("vals"), py::arg("labels"),
+     py::arg("B"), py::arg("loss_type"), py::arg("margin"), py::arg("metrics"), py::arg("hist"),
      py::arg("nbins"), py::arg("lanes") = 0);
   m.def("linear_bwd", [](Tensor pos_s, Tensor segid, int64_t n, optional<Tensor> rows, int width,
                          optional<Tensor> vals, Tensor coef, optional<Tensor> coef2, Tensor grad,

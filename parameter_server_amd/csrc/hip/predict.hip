@@ -22,36 +22,12 @@
 // the same bits on every run: a lane sums its occurrences in index order and the group
 // reduces in a fixed xor tree.
 #include "predict.h"
-#include "kv_slot.cuh"
 #include "loss.cuh"
+#include "probe.cuh"
 #include <stdexcept>
 #include <string>
 
 namespace psamd {
-
-// {key, w, z} of a slot as one 16-byte load (Slot is 32-byte aligned)
-__device__ __forceinline__ uint4 load_slot_head(const Slot* __restrict__ slots, uint64_t idx) {
-  return *reinterpret_cast<const uint4*>(slots + idx);
-}
-__device__ __forceinline__ uint64_t head_key(const uint4& v) {
-  return ((uint64_t)v.y << 32) | v.x;
-}
-
-// The rest of a probe chain whose first slot (idx) held another key. Read-only.
-__device__ __forceinline__ float probe_on(const Slot* __restrict__ slots, uint64_t mask,
-                                          uint64_t idx, uint64_t h) {
-  // TRIP BOUND: at most mask + 1 slots are visited in all (the first probe was slot 0 of
-  // the chain), as in resolve_key: on a table without an empty slot an absent key's
-  // chain never meets kEmptyKey, and without the bound this loop would not end.
-  for (uint64_t probe = 1; probe <= mask; ++probe) {
-    idx = (idx + 1) & mask;
-    const uint4 v = load_slot_head(slots, idx);
-    const uint64_t k = head_key(v);
-    if (k == h) return __uint_as_float(v.z);
-    if (k == kEmptyKey) return 0.f;
-  }
-  return 0.f;
-}
 
 template <int kLPR, int kBatch, bool kHasRowPtr, bool kMix32>
 __global__ void __launch_bounds__(256)
@@ -107,7 +83,7 @@ predict_kernel(const Slot* __restrict__ slots, uint64_t mask, uint64_t home_base
       for (int j = 0; j < kBatch; ++j) {
         const uint64_t k = head_key(v[j]);
         float w = k == h[j] ? __uint_as_float(v[j].z) : 0.f;
-        if (ok[j] && k != h[j] && k != kEmptyKey) w = probe_on(slots, mask, idx[j], h[j]);
+        if (ok[j] && k != h[j] && k != kEmptyKey) probe_on(slots, mask, idx[j], h[j], w);
         m += ok[j] ? w * x[j] : 0.f;
       }
     }

@@ -21,7 +21,9 @@ the sparse-LR segmented reduction -> AdaGrad (proximal L2) on w.
 
 ``step(..., row_ptr=)`` takes CSR minibatches (rows of any width, optional values): the
 same step with ``fm_csr`` (fm.hip: a group of 16 / 32 / 64 lanes per row) in place of
-``fm_fwd_bwd``; ``predict`` on a GPU trainer runs its forward-only form.
+``fm_fwd_bwd``; ``predict`` on a GPU trainer runs its forward-only form. ``scorer()`` gives
+held-out loss / accuracy / AUC through the fused scoring kernel (models/scorer.py
+``FMScorer``, fm_predict.hip), for every ``embedding_dim``.
 """
 from __future__ import annotations
 
@@ -331,6 +333,20 @@ class FMTrainer(EmbeddingPS):
         s = torch.zeros(B, D).index_add_(0, r, V)
         q = torch.zeros(B).index_add_(0, r, (V * V).sum(1))
         return torch.zeros(B).index_add_(0, r, w) + 0.5 * ((s * s).sum(1) - q)
+
+    def scorer(self):
+        """An ``FMScorer`` on this trainer's own shard (no copy): held-out loss, accuracy and
+        AUC through the fused scoring kernel, for every ``embedding_dim`` (``predict`` keeps
+        its D limit on the GPU). G == 1. Nothing is synchronised here: score on the stream
+        the steps run on, after them."""
+        if self.G != 1:
+            raise NotImplementedError(
+                "scorer() reads the local shard (G == 1); score a sharded model with "
+                "FMScorer.from_state_dict(FMTrainer.merge_state_dicts(<every rank's "
+                "state_dict()>))")
+        from .scorer import FMScorer
+
+        return FMScorer.from_shard(self.shard, self.bits)
 
     def progress(self, reset: bool = True) -> dict:
         self._xe_check()

@@ -12,9 +12,10 @@ from __future__ import annotations
 
 import torch
 
+from ..ops.embedding import EmbeddingShard
 from ..ops.keymix import mix
 from ..ops.kv_table import KVTable, next_pow2
-from ..ops.score import ScoreAccum, auc_from_counts, score
+from ..ops.score import ScoreAccum, auc_from_counts, fm_score, score
 
 
 class ModelScorer:
@@ -73,19 +74,21 @@ class ModelScorer:
         return sc
 
     # ------------------------------------------------------------ scoring
+    def _score(self, keys, **kw):
+        """The op behind every method below (``FMScorer`` puts its own here)."""
+        return score(self.table, keys, self.bits, **kw)
+
     def predict(self, keys: torch.Tensor, *, row_ptr=None, width=None, vals=None,
                 lanes: int = 0) -> torch.Tensor:
         """Margins only (nothing accumulated)."""
-        return score(self.table, keys, self.bits, row_ptr=row_ptr, width=width, vals=vals,
-                     lanes=lanes)
+        return self._score(keys, row_ptr=row_ptr, width=width, vals=vals, lanes=lanes)
 
     def score(self, keys, labels, *, row_ptr=None, width=None, vals=None, margins=True,
               lanes: int = 0):
         """Margins of one labelled minibatch; its sums and bins go into the accumulator."""
         B = row_ptr.numel() - 1 if row_ptr is not None else keys.numel() // int(width)
-        return score(self.table, keys, self.bits, row_ptr=row_ptr, width=width, vals=vals,
-                     labels=labels, margins=margins, acc=self.acc, loss=self.loss, B=B,
-                     lanes=lanes)
+        return self._score(keys, row_ptr=row_ptr, width=width, vals=vals, labels=labels,
+                           margins=margins, acc=self.acc, loss=self.loss, B=B, lanes=lanes)
 
     def score_batch(self, b, margins: bool = False):
         """One ``DeviceBatch`` of a ``DeviceFeeder``."""
@@ -94,8 +97,8 @@ class ModelScorer:
             kw = dict(row_ptr=b.row_ptr[:b.rows + 1])
         else:
             kw = dict(width=b.width)
-        return score(self.table, keys, self.bits, vals=b.vals, labels=b.labels, margins=margins,
-                     acc=self.acc, loss=self.loss, B=b.rows, **kw)
+        return self._score(keys, vals=b.vals, labels=b.labels, margins=margins, acc=self.acc,
+                           loss=self.loss, B=b.rows, **kw)
 
     def evaluate(self, feeder, pass_index: int = 0, predictions=None) -> "ModelScorer":
         """Drain one pass of a ``DeviceFeeder`` (each batch released behind its launch).
@@ -139,3 +142,41 @@ class ModelScorer:
         return {"examples": int(n), "loss": sums[0] / n if n else float("nan"),
                 "accuracy": sums[1] / n if n else float("nan"), "auc": auc,
                 "auc_tie_bound": tie}
+
+
+class FMScorer(ModelScorer):
+    """``ModelScorer`` for a factorization machine (models/fm.py): the model is an
+    ``EmbeddingShard`` -- the KV table with the wide weights and the bf16 factor rows at the
+    same slot index -- and every minibatch is one launch of the fused probe + factor kernel
+    (ops/score.py ``fm_score``, csrc/hip/fm_predict.hip), for rows of any width and every
+    ``embedding_dim`` the trainer accepts (multiples of 8 up to 128). ``predict``, ``score``,
+    ``score_batch``, ``evaluate``, ``totals`` and ``result`` are ``ModelScorer``'s."""
+
+    def __init__(self, shard: EmbeddingShard, bits: int, loss="logit"):
+        super().__init__(shard.table, bits, loss)
+        self.shard = shard
+
+    @classmethod
+    def from_shard(cls, shard: EmbeddingShard, bits: int, loss="logit") -> "FMScorer":
+        """Alias an existing shard (no copy). The caller orders its own updates before the
+        scoring launches (``FMTrainer.scorer``: the same stream)."""
+        return cls(shard, bits, loss)
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, device, capacity: int | None = None) -> "FMScorer":
+        """A snapshot of ``FMTrainer.state_dict`` (or ``merge_state_dicts`` of the ranks'
+        snapshots: the keys are raw ids, so any world size wrote it) in a shard of its own
+        at load <= 0.5; key width and factor dimension come from the snapshot."""
+        if str(sd.get("model")) != "FMTrainer":
+            raise ValueError(f"snapshot of a {sd.get('model')}, not an FMTrainer")
+        bits, dim = int(sd["bits"]), int(sd["dim"])
+        n = sd["keys"].numel()
+        shard = EmbeddingShard(capacity or next_pow2(max(64, 2 * n)), dim, device)
+        if n:  # (check_ok inside: a capacity too small raises 'KVTable full')
+            mk = mix(sd["keys"].cpu().contiguous(), bits)
+            shard.load_state(mk, sd["w"], sd["z"], sd["n"], sd["rows"], sd["acc"],
+                             cnt=sd.get("cnt"))
+        return cls(shard, bits)
+
+    def _score(self, keys, **kw):
+        return fm_score(self.shard, keys, self.bits, **kw)

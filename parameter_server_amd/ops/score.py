@@ -93,19 +93,79 @@ def score(table, keys: torch.Tensor, bits: int, *, row_ptr=None, width=None, val
     rows = _rows_of(B, int(width or 0), rp, dev)
     m.zero_().index_add_(0, rows, contrib[:rows.numel()])
     if acc is not None:
-        y = labels[:B].float()
-        # (terms in f64: torch's vectorised f32 softplus differs in the last bit between a
-        # row's place in the SIMD body and in the scalar tail, so f32 terms would make the
-        # sum depend on how the rows are cut into minibatches)
-        lo, _, _ = loss_terms_torch(m.double(), y.double(), L)
-        mt = acc.metrics  # CPU code adds into stripe 0
-        mt[0] += float(lo.sum())
-        mt[1] += float(((y > 0) == (m > 0)).double().sum())
-        mt[2] += float(B)
-        p = torch.sigmoid(m)
-        b = torch.clamp((p * AUC_BINS).long(), 0, AUC_BINS - 1)
-        off = torch.where(y > 0, AUC_BINS, 0)
-        acc.hist[:2 * AUC_BINS] += torch.bincount(b + off, minlength=2 * AUC_BINS)
+        _accumulate(acc, m, labels, B, L)
+    return m if margins else None
+
+
+def _accumulate(acc: ScoreAccum, m: torch.Tensor, labels: torch.Tensor, B: int, L: int):
+    """The CPU path's sums and bins of B margins ``m`` into ``acc``."""
+    y = labels[:B].float()
+    # (terms in f64: torch's vectorised f32 softplus differs in the last bit between a
+    # row's place in the SIMD body and in the scalar tail, so f32 terms would make the
+    # sum depend on how the rows are cut into minibatches)
+    lo, _, _ = loss_terms_torch(m.double(), y.double(), L)
+    mt = acc.metrics  # CPU code adds into stripe 0
+    mt[0] += float(lo.sum())
+    mt[1] += float(((y > 0) == (m > 0)).double().sum())
+    mt[2] += float(B)
+    p = torch.sigmoid(m)
+    b = torch.clamp((p * AUC_BINS).long(), 0, AUC_BINS - 1)
+    off = torch.where(y > 0, AUC_BINS, 0)
+    acc.hist[:2 * AUC_BINS] += torch.bincount(b + off, minlength=2 * AUC_BINS)
+
+
+def fm_score(shard, keys: torch.Tensor, bits: int, *, row_ptr=None, width=None, vals=None,
+             labels=None, margins: bool = True, acc: ScoreAccum | None = None, loss="logit",
+             B: int | None = None, lanes: int = 0):
+    """``score`` for a factorization machine: ``shard`` is an ``EmbeddingShard`` (the KV
+    table with the wide weights and the bf16 factor rows at the same slot index, any
+    ``dim`` that is a multiple of 8 up to 128); margin = x.w + 1/2 sum_f [(sum_i x_i
+    v_if)^2 - sum_i x_i^2 v_if^2], a key the model does not hold contributing nothing.
+    GPU: one ``fm_predict_rows`` launch (csrc/hip/fm_predict.hip); CPU: the PyTorch ops of
+    ``FMTrainer.predict``. ``lanes``: lanes per row on the GPU (0: from nnz / B; 16, 32, 64)."""
+    if (row_ptr is None) == (not width):
+        raise ValueError("fm_score needs row_ptr or a fixed width, not both")
+    if acc is not None and labels is None:
+        raise ValueError("fm_score: an accumulator needs labels")
+    keys = keys.contiguous()
+    nnz = keys.numel()
+    if B is None:
+        B = row_ptr.numel() - 1 if row_ptr is not None else nnz // int(width)
+    dev = keys.device
+    L = loss_id(loss)
+    table = shard.table
+    if is_gpu(keys):
+        m = torch.empty(B, dtype=torch.float32, device=dev) if margins else None
+        if B:
+            hipops().fm_predict_rows(table.slots, table.home_base, table.home_m, shard.rows, keys,
+                                     bits, row_ptr, int(width or 0), vals, labels, B, L, m,
+                                     acc.metrics if acc is not None else None,
+                                     acc.hist if acc is not None else None, AUC_BINS, lanes)
+        return m
+    if B == 0:
+        return torch.empty(0, dtype=torch.float32) if margins else None
+    D = shard.dim
+    slot, w = table.resolve(mix(keys, bits), insert=False)
+    ok = slot >= 0
+    w = torch.where(ok, w, torch.zeros_like(w))
+    V = torch.zeros(nnz, D, device=dev)
+    V[ok] = shard.rows[slot[ok]].float()
+    if vals is not None:
+        V = V * vals.float()[:, None]
+        w = w * vals.float()
+    if row_ptr is None:
+        S = int(width)
+        V = V[:B * S].reshape(B, S, D)
+        s = V.sum(1)
+        m = w[:B * S].reshape(B, S).sum(1) + 0.5 * (s * s - (V * V).sum(1)).sum(1)
+    else:
+        r = torch.repeat_interleave(torch.arange(B), row_ptr[1:B + 1] - row_ptr[:B])
+        n = r.numel()
+        s = torch.zeros(B, D).index_add_(0, r, V[:n])
+        q = torch.zeros(B).index_add_(0, r, (V[:n] * V[:n]).sum(1))
+        m = torch.zeros(B).index_add_(0, r, w[:n]) + 0.5 * ((s * s).sum(1) - q)
+    if acc is not None:
+        _accumulate(acc, m, labels, B, L)
     return m if margins else None
 
 
