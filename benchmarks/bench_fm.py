@@ -180,8 +180,69 @@ def csr_mode(args):
     }), flush=True)
 
 
+def ffm_mode(args):
+    """1 GPU: the field-aware FM step (models/ffm.py, ffm.hip) on Criteo-shaped minibatches, for
+    k = 2 with one field per slot (rows of 80) and k = 4 with the 13 integer slots on one field
+    (F = 27, rows of 112). Beside it, alternated window by window in this one process: the same
+    trainer with the kernel replaced by its vectorised PyTorch form on CUDA tensors (expand +
+    ``_fwd_bwd_torch``: what there is without the kernel), and the plain FM step at D = 16 as
+    context. Step times by a host clock around synchronised windows."""
+    from parameter_server_amd.models.ffm import FFMConfig, FFMTrainer
+    from parameter_server_amd.models.fm import FMConfig, FMTrainer
+    from parameter_server_amd.ops import embedding as E
+    from parameter_server_amd.ops.synthetic import criteo_batch
+
+    class TorchFFM(FFMTrainer):
+        def _fwd_bwd_hip(self, rows_src, rows_idx, vals, B, loc, w_wide, labels):
+            S = self.cfg.slots
+            X0 = E.expand(loc.local_col, B * S, rows_src, idx=rows_idx)
+            return self._fwd_bwd_torch(X0, vals, B, S, loc.local_col, w_wide, labels)
+
+    dev = torch.device("cuda", 0)
+    B, N = args.minibatch, int(args.num_features)
+    slots = min(args.table_slots, 1 << 24)  # five tables side by side
+    crit = [criteo_batch(B, seed=77, row0=i * B, num_features=N, device=dev) for i in range(8)]
+    common = dict(localize=args.localize, num_features=N, minibatch=B, table_capacity=slots, seed=0)
+    shapes = {"k2_F39": dict(k=2), "k4_F27": dict(k=4, fields=[0] * 13 + list(range(1, 27)))}
+    trainers = {"fm_D16": FMTrainer(FMConfig(embedding_dim=16, **common), device=dev)}
+    for tag, kw in shapes.items():
+        trainers[f"ffm_{tag}"] = FFMTrainer(FFMConfig(**kw, **common), device=dev)
+        trainers[f"ffm_{tag}_torch"] = TorchFFM(FFMConfig(**kw, **common), device=dev)
+
+    def window(tr):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            tr.step(*crit[i % len(crit)])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps * 1e3
+
+    for tr in trainers.values():
+        for i in range(args.warmup):
+            tr.step(*crit[i % len(crit)])
+    ms = {name: [] for name in trainers}
+    for r in range(args.repeats):
+        for name, tr in trainers.items():
+            ms[name].append(window(tr))
+        print(f"window {r}: " + "  ".join(f"{n} {v[-1]:.3f} ms" for n, v in ms.items()),
+              flush=True)
+    med = {n: sorted(v)[len(v) // 2] for n, v in ms.items()}
+    print(json.dumps({
+        "metric": "FFM step time (ffm.hip) vs the same step with the PyTorch forward / backward, "
+                  "and the FM step at D = 16, 1 GPU",
+        "unit": "ms/step (median of windows)", "steps_per_window": args.steps,
+        "windows": args.repeats, "minibatch": B, "slots": 39, "median_ms": med,
+        "min_ms": {n: min(v) for n, v in ms.items()}, "max_ms": {n: max(v) for n, v in ms.items()},
+        "torch_over_hip": {t: med[f"ffm_{t}_torch"] / med[f"ffm_{t}"] for t in shapes},
+        "row_width": {t: trainers[f"ffm_{t}"].Dr for t in shapes},
+        "train": {n: tr.progress() for n, tr in trainers.items()}, "all_ms": ms}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ffm", action="store_true",
+                    help="1 GPU: the field-aware FM step (k = 2, and k = 4 on 27 fields) vs the same "
+                         "step with the PyTorch forward / backward and the FM step, alternated")
     ap.add_argument("--csr", action="store_true",
                     help="1 GPU: fixed-width step vs the row_ptr step on the same minibatches, "
                          "alternated, and an rcv1-shaped valued minibatch")
@@ -204,6 +265,8 @@ def main():
     ap.add_argument("--prefetch", type=int, default=1,
                     help="generate + localise minibatch t+1 on a side stream during step t")
     args = ap.parse_args()
+    if args.ffm:
+        return ffm_mode(args)
     if args.csr:
         return csr_mode(args)
     if args.score:

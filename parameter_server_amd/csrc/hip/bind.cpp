@@ -665,4 +665,5 @@ PYBIND11_MODULE(_hipops, m) {
   register_dense(m);
   register_scoretext(m);
   register_slotsplit(m);
+  register_ffm(m);
 }

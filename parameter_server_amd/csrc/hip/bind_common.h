@@ -34,6 +34,7 @@ void register_linear(py::module_& m);    // linear / predict / FM, the generator
 void register_dense(py::module_& m);     // Darlin BCD, GEMMs, embedding, spmv
 void register_scoretext(py::module_& m); // prediction lines
 void register_slotsplit(py::module_& m); // split by feature group
+void register_ffm(py::module_& m);       // field-aware FM
 
 inline hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 

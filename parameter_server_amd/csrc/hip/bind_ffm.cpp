@@ -1,0 +1,81 @@
+// Bindings of the field-aware factorization machine (ffm.hip).
+#include "bind_common.h"
+#include "ffm.h"
+
+using namespace psamd_bind;
+
+namespace {
+
+// what the two ops share: the geometry, the factor rows, the occurrences. `fields` must
+// outlive the launch call (the launcher reads it on the host).
+psamd::Ffm check_ffm(const Tensor& rows, const optional<Tensor>& idx, const optional<Tensor>& vals,
+                     int64_t B, int S, const std::vector<int32_t>& fields, int F, int k,
+                     const optional<Tensor>& local_col, const Tensor& w_local) {
+  psamd::Ffm a = {};
+  chk(rows, at::kBFloat16, "rows");
+  chk(w_local, at::kFloat, "w_local");
+  check(rows.dim() == 2, "rows [R, Dr]");
+  check(S >= 1 && S <= 64, "ffm: 1..64 positions per row");
+  check(k == 2 || k == 4 || k == 8, "ffm: k in {2, 4, 8}");
+  a.Dr = (int)rows.size(1);
+  check(rows.size(1) % 8 == 0 && rows.size(1) <= 128 && F >= 1 && (int64_t)F * k <= rows.size(1),
+        "ffm: rows of F * k <= Dr <= 128 columns, Dr % 8 == 0");
+  check((int64_t)fields.size() == S, "ffm: one field per position");
+  for (int32_t f : fields) check(f >= 0 && f < F, "ffm: field outside [0, F)");
+  check(B >= 0 && B * S < (int64_t(1) << 31), "ffm: 0 <= B * S < 2^31");
+  a.B = B;
+  a.S = S;
+  a.F = F;
+  a.k = k;
+  a.fields = fields.data();
+  a.local_col = optr<int32_t>(local_col, at::kInt, "local_col");
+  if (a.local_col) check(local_col->numel() >= B * S, "local_col too small");
+  a.vals = optr<float>(vals, at::kFloat, "vals");
+  if (a.vals) check(vals->numel() >= B * S, "vals too small");
+  a.rows = rows.data_ptr();
+  a.rows_cap = rows.size(0);
+  a.idx = optr<int64_t>(idx, at::kLong, "idx");
+  a.idx_cap = a.idx ? idx->numel() : 0;
+  a.w_local = ptr<float>(w_local);
+  a.w_cap = w_local.numel();
+  return a;
+}
+
+}  // namespace
+
+void psamd_bind::register_ffm(py::module_& m) {
+  // rows [R, Dr] bf16 read through local_col (None: column = position) and idx (None: the
+  // column is the row); fields [S] ints in [0, F), one map for all rows
+  m.def("ffm_fwd_bwd", [](Tensor rows, optional<Tensor> idx, optional<Tensor> vals, int64_t B,
+                          int S, std::vector<int32_t> fields, int F, int k,
+                          optional<Tensor> local_col, Tensor w_local, Tensor labels, Tensor coef,
+                          Tensor dX0, Tensor metrics, optional<Tensor> hist, int nbins) {
+    psamd::Ffm a = check_ffm(rows, idx, vals, B, S, fields, F, k, local_col, w_local);
+    chk(labels, at::kFloat, "labels");
+    chk(coef, at::kFloat, "coef");
+    chk(dX0, at::kBFloat16, "dX0");
+    chk(metrics, at::kDouble, "metrics");
+    check(labels.numel() >= B && coef.numel() >= B, "labels/coef too small");
+    check(dX0.numel() >= B * S * a.Dr, "dX0 too small");
+    check(metrics.numel() >= 3, "metrics[3]");
+    a.hist = optr<uint32_t>(hist, at::kInt, "hist");
+    if (a.hist) check(nbins > 0 && hist->numel() >= 2 * nbins, "hist too small");
+    a.labels = ptr<float>(labels);
+    a.coef = ptr<float>(coef);
+    a.dX0 = dX0.data_ptr();
+    a.metrics = ptr<double>(metrics);
+    a.nbins = nbins;
+    a.acc_stripes = acc_stripes_of(metrics);
+    psamd::ffm_fwd_bwd(a, cur_stream());
+  });
+  // the forward-only form: margins [B] and nothing else
+  m.def("ffm_margins", [](Tensor rows, optional<Tensor> idx, optional<Tensor> vals, int64_t B,
+                          int S, std::vector<int32_t> fields, int F, int k,
+                          optional<Tensor> local_col, Tensor w_local, Tensor margins) {
+    psamd::Ffm a = check_ffm(rows, idx, vals, B, S, fields, F, k, local_col, w_local);
+    chk(margins, at::kFloat, "margins");
+    check(margins.numel() >= B, "margins too small");
+    a.margins = ptr<float>(margins);
+    psamd::ffm_margins(a, cur_stream());
+  });
+}

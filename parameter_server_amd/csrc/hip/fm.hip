@@ -20,22 +20,13 @@
 // fm_csr_kernel (a lane group per row, CSR rows of any width, D in {8, 16, 32}; with
 // its forward-only form for scoring).
 #include "fm.h"
+#include "bf16.cuh"
 #include "common.cuh"
 
 #include <algorithm>
 #include <stdexcept>
 
 namespace psamd {
-
-namespace {
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) {  // round to nearest even
-  const uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-}  // namespace
 
 __global__ void __launch_bounds__(256)
 fm_fwd_bwd_kernel(const uint16_t* __restrict__ X0, const float* __restrict__ vals, int64_t B,

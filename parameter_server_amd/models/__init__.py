@@ -1,8 +1,9 @@
 """Model families trained through the parameter server."""
+from .ffm import FFMConfig, FFMTrainer
 from .fm import FMConfig, FMTrainer
 from .scorer import FMScorer, ModelScorer
 from .sparse_lr import SparseLRConfig, SparseLRTrainer
 from .wide_deep import WideDeepConfig, WideDeepTrainer
 
 __all__ = ["SparseLRConfig", "SparseLRTrainer", "WideDeepConfig", "WideDeepTrainer", "FMConfig",
-           "FMTrainer", "ModelScorer", "FMScorer"]
+           "FMTrainer", "FFMConfig", "FFMTrainer", "ModelScorer", "FMScorer"]
