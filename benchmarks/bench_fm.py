@@ -186,7 +186,10 @@ def ffm_mode(args):
     (F = 27, rows of 112). Beside it, alternated window by window in this one process: the same
     trainer with the kernel replaced by its vectorised PyTorch form on CUDA tensors (expand +
     ``_fwd_bwd_torch``: what there is without the kernel), and the plain FM step at D = 16 as
-    context. Step times by a host clock around synchronised windows."""
+    context. The k = 2 shape also runs through the CSR step (ffm_csr.hip, a field id per
+    occurrence): (a) the same full-width minibatches, against the fixed-width step above, and
+    (b) the minibatches with each slot present with probability 0.75 (as bench_csr.py).
+    Step times by a host clock around synchronised windows."""
     from parameter_server_amd.models.ffm import FFMConfig, FFMTrainer
     from parameter_server_amd.models.fm import FMConfig, FMTrainer
     from parameter_server_amd.ops import embedding as E
@@ -209,21 +212,46 @@ def ffm_mode(args):
         trainers[f"ffm_{tag}"] = FFMTrainer(FFMConfig(**kw, **common), device=dev)
         trainers[f"ffm_{tag}_torch"] = TorchFFM(FFMConfig(**kw, **common), device=dev)
 
-    def window(tr):
+    routes = {name: (lambda i, tr=tr: tr.step(*crit[i % len(crit)]))
+              for name, tr in trainers.items()}
+    # the CSR step: full rows (row_ptr = 39 b, fields = the slot index), then missing slots
+    slot_of = torch.arange(39, dtype=torch.int32, device=dev).repeat(B)
+    uniform = torch.arange(B + 1, device=dev) * 39
+    g = torch.Generator(device=dev).manual_seed(5)
+    sparse = []
+    for k39, lab in crit:
+        keep = torch.rand(B * 39, device=dev, generator=g) < 0.75
+        rp = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        rp[1:] = torch.cumsum(keep.view(B, 39).sum(1), 0)
+        sparse.append((k39[keep], lab, rp, slot_of[keep]))
+    for tag in ("ffm_k2_F39_csr_full", "ffm_k2_F39_csr_missing"):
+        trainers[tag] = FFMTrainer(FFMConfig(k=2, **common), device=dev)
+
+    def csr_full(i, tr=trainers["ffm_k2_F39_csr_full"]):
+        k39, lab = crit[i % len(crit)]
+        tr.step(k39, lab, row_ptr=uniform, fields=slot_of)
+
+    def csr_missing(i, tr=trainers["ffm_k2_F39_csr_missing"]):
+        k, lab, rp, fl = sparse[i % len(sparse)]
+        tr.step(k, lab, row_ptr=rp, fields=fl)
+
+    routes["ffm_k2_F39_csr_full"], routes["ffm_k2_F39_csr_missing"] = csr_full, csr_missing
+
+    def window(fn):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            tr.step(*crit[i % len(crit)])
+            fn(i)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / args.steps * 1e3
 
-    for tr in trainers.values():
+    for fn in routes.values():
         for i in range(args.warmup):
-            tr.step(*crit[i % len(crit)])
-    ms = {name: [] for name in trainers}
+            fn(i)
+    ms = {name: [] for name in routes}
     for r in range(args.repeats):
-        for name, tr in trainers.items():
-            ms[name].append(window(tr))
+        for name, fn in routes.items():
+            ms[name].append(window(fn))
         print(f"window {r}: " + "  ".join(f"{n} {v[-1]:.3f} ms" for n, v in ms.items()),
               flush=True)
     med = {n: sorted(v)[len(v) // 2] for n, v in ms.items()}
@@ -234,6 +262,8 @@ def ffm_mode(args):
         "windows": args.repeats, "minibatch": B, "slots": 39, "median_ms": med,
         "min_ms": {n: min(v) for n, v in ms.items()}, "max_ms": {n: max(v) for n, v in ms.items()},
         "torch_over_hip": {t: med[f"ffm_{t}_torch"] / med[f"ffm_{t}"] for t in shapes},
+        "csr_over_fixed": med["ffm_k2_F39_csr_full"] / med["ffm_k2_F39"],
+        "csr_missing_nnz": [int(x[0].numel()) for x in sparse[:2]],
         "row_width": {t: trainers[f"ffm_{t}"].Dr for t in shapes},
         "train": {n: tr.progress() for n, tr in trainers.items()}, "all_ms": ms}), flush=True)
 

@@ -37,7 +37,7 @@ CXX = shutil.which("g++") or "c++"
 # of the whole unit, header functions included, so that everything still inlines (fm.hip
 # says the same per kernel, with a target attribute).
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-NO_PACKED_F32_UNITS = {"fm_predict.hip", "ffm.hip"}
+NO_PACKED_F32_UNITS = {"fm_predict.hip", "ffm.hip", "ffm_csr.hip"}
 
 
 def _py_includes() -> list[str]:

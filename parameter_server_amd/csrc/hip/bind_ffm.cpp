@@ -41,9 +41,87 @@ psamd::Ffm check_ffm(const Tensor& rows, const optional<Tensor>& idx, const opti
   return a;
 }
 
+// the CSR ops: row_ptr [B + 1] int64, fld [nnz] int32 (device), everything per occurrence
+// holds at least nnz entries
+psamd::FfmCsr check_ffm_csr(const Tensor& row_ptr, const Tensor& fld, int64_t nnz,
+                            const Tensor& rows, const optional<Tensor>& idx,
+                            const optional<Tensor>& vals, int64_t B, int T, int F, int k,
+                            const optional<Tensor>& local_col, const Tensor& w_local) {
+  psamd::FfmCsr a = {};
+  chk(row_ptr, at::kLong, "row_ptr");
+  chk(fld, at::kInt, "fields");
+  chk(rows, at::kBFloat16, "rows");
+  chk(w_local, at::kFloat, "w_local");
+  check(rows.dim() == 2, "rows [R, Dr]");
+  check(T >= 1 && T <= 64, "ffm_csr: a tile of 1..64 rows");
+  check(k == 2 || k == 4 || k == 8, "ffm_csr: k in {2, 4, 8}");
+  check(rows.size(1) % 8 == 0 && rows.size(1) <= 128 && F >= 1 && (int64_t)F * k <= rows.size(1),
+        "ffm_csr: rows of F * k <= Dr <= 128 columns, Dr % 8 == 0");
+  check(B >= 0 && nnz >= 0 && nnz < (int64_t(1) << 31), "ffm_csr: B >= 0, 0 <= nnz < 2^31");
+  check(row_ptr.numel() >= B + 1, "row_ptr too small");
+  check(fld.numel() >= nnz, "fields too small");
+  a.row_ptr = ptr<int64_t>(row_ptr);
+  a.fld = ptr<int32_t>(fld);
+  a.B = B;
+  a.nnz = nnz;
+  a.T = T;
+  a.F = F;
+  a.k = k;
+  a.Dr = (int)rows.size(1);
+  a.local_col = optr<int32_t>(local_col, at::kInt, "local_col");
+  if (a.local_col) check(local_col->numel() >= nnz, "local_col too small");
+  a.vals = optr<float>(vals, at::kFloat, "vals");
+  if (a.vals) check(vals->numel() >= nnz, "vals too small");
+  a.rows = rows.data_ptr();
+  a.rows_cap = rows.size(0);
+  a.idx = optr<int64_t>(idx, at::kLong, "idx");
+  a.idx_cap = a.idx ? idx->numel() : 0;
+  a.w_local = ptr<float>(w_local);
+  a.w_cap = w_local.numel();
+  return a;
+}
+
 }  // namespace
 
 void psamd_bind::register_ffm(py::module_& m) {
+  // CSR rows with a field per occurrence (ffm_csr.hip): rows of up to T positions on the LDS
+  // tile, wider ones on the global-memory path; also writes row_of [nnz]
+  m.def("ffm_csr", [](Tensor row_ptr, Tensor fld, int64_t nnz, Tensor rows, optional<Tensor> idx,
+                      optional<Tensor> vals, int64_t B, int T, int F, int k,
+                      optional<Tensor> local_col, Tensor w_local, Tensor labels, Tensor coef,
+                      Tensor dX0, Tensor row_of, Tensor metrics, optional<Tensor> hist, int nbins) {
+    psamd::FfmCsr a = check_ffm_csr(row_ptr, fld, nnz, rows, idx, vals, B, T, F, k, local_col,
+                                    w_local);
+    chk(labels, at::kFloat, "labels");
+    chk(coef, at::kFloat, "coef");
+    chk(dX0, at::kBFloat16, "dX0");
+    chk(row_of, at::kInt, "row_of");
+    chk(metrics, at::kDouble, "metrics");
+    check(labels.numel() >= B && coef.numel() >= B, "labels/coef too small");
+    check(dX0.numel() >= nnz * a.Dr, "dX0 too small");
+    check(row_of.numel() >= nnz, "row_of too small");
+    check(metrics.numel() >= 3, "metrics[3]");
+    a.hist = optr<uint32_t>(hist, at::kInt, "hist");
+    if (a.hist) check(nbins > 0 && hist->numel() >= 2 * nbins, "hist too small");
+    a.labels = ptr<float>(labels);
+    a.coef = ptr<float>(coef);
+    a.dX0 = dX0.data_ptr();
+    a.row_of = ptr<int32_t>(row_of);
+    a.metrics = ptr<double>(metrics);
+    a.nbins = nbins;
+    a.acc_stripes = acc_stripes_of(metrics);
+    psamd::ffm_csr(a, cur_stream());
+  });
+  m.def("ffm_csr_margins", [](Tensor row_ptr, Tensor fld, int64_t nnz, Tensor rows,
+                              optional<Tensor> idx, optional<Tensor> vals, int64_t B, int T, int F,
+                              int k, optional<Tensor> local_col, Tensor w_local, Tensor margins) {
+    psamd::FfmCsr a = check_ffm_csr(row_ptr, fld, nnz, rows, idx, vals, B, T, F, k, local_col,
+                                    w_local);
+    chk(margins, at::kFloat, "margins");
+    check(margins.numel() >= B, "margins too small");
+    a.margins = ptr<float>(margins);
+    psamd::ffm_csr_margins(a, cur_stream());
+  });
   // rows [R, Dr] bf16 read through local_col (None: column = position) and idx (None: the
   // column is the row); fields [S] ints in [0, F), one map for all rows
   m.def("ffm_fwd_bwd", [](Tensor rows, optional<Tensor> idx, optional<Tensor> vals, int64_t B,

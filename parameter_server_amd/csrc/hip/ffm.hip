@@ -28,10 +28,11 @@
 // * Loss, accuracy, AUC bin, coef: once per row by lane 0, as fm_csr_kernel.
 //
 // The tile belongs to its wave: the only block barrier is the one after the field lists are
-// copied, before the row loop. kBwd = false writes margins[B] and nothing else.
+// copied, before the row loop. kBwd = false writes margins[B] and nothing else. The staging,
+// the item loop's body, the store and the per-row loss live in ffm_tile.cuh, shared with the
+// CSR form (ffm_csr.hip: a field per occurrence, lists built per row in the wave).
 #include "ffm.h"
-#include "bf16.cuh"
-#include "common.cuh"
+#include "ffm_tile.cuh"
 
 #include <algorithm>
 #include <stdexcept>
@@ -42,8 +43,8 @@ namespace psamd {
 namespace {
 
 constexpr int kMapWords = 49;   // bytes: fld[64] | pos[64] | off[65 -> 68]
-constexpr int kMapChunks = 16;  // the block's copy: 256 B of LDS in front of the tiles
-constexpr int kXsChunks = 16;   // x of a wave's 64 positions behind its tile
+constexpr int kMapChunks = kFfmMapChunks;  // the block's copy: 256 B of LDS in front of the tiles
+constexpr int kXsChunks = kFfmXsChunks;
 
 struct FfmK {
   Ffm a;
@@ -51,71 +52,11 @@ struct FfmK {
   uint32_t map[kMapWords];
 };
 
-struct FfmLds {  // a wave's view of the block's LDS
-  const uint8_t *fld, *pos, *off;
-  uint4* tile;
-  float* xs;
-};
-
-// LDS written by some lanes of the wave is read by others of the same wave
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-template <int K>
-struct alignas(K * 2) FfmVec {  // k bf16 of one field, as the tile holds them
-  uint32_t w[K / 2];
-};
-
-// G of item t = (i, c) and its share x_i <tile[i][c], G> of the pair sum
-template <int K>
-__device__ __forceinline__ float ffm_item(const FfmK& p, const FfmLds& l, int t, float (&G)[8]) {
+// dX0[b * S + i][c] of item t = (i, c)
+__device__ __forceinline__ void ffm_store_item(const FfmK& p, const FfmLds& l, int64_t b, int t,
+                                               float coef, const float (&G)[8]) {
   const int c = t / p.a.S, i = t - c * p.a.S;
-  const char* col = reinterpret_cast<const char*>(l.tile) + (int)l.fld[i] * (K * 2);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) G[e] = 0.f;
-#pragma unroll
-  for (int u = 0; u < 8 / K; ++u) {
-    const int f = c * (8 / K) + u;
-    if (f < p.a.F) {
-      const int q1 = l.off[f + 1];
-      for (int q = l.off[f]; q < q1; ++q) {
-        const int j = l.pos[q];
-        if (j == i) continue;
-        const float xj = l.xs[j];
-        const FfmVec<K> v = *reinterpret_cast<const FfmVec<K>*>(col + j * p.Q * 16);
-#pragma unroll
-        for (int e = 0; e < K / 2; ++e) {
-          G[u * K + 2 * e] = fmaf(xj, __uint_as_float(v.w[e] << 16), G[u * K + 2 * e]);
-          G[u * K + 2 * e + 1] = fmaf(xj, __uint_as_float(v.w[e] & 0xffff0000u), G[u * K + 2 * e + 1]);
-        }
-      }
-    }
-  }
-  const uint4 own = l.tile[i * p.Q + c];
-  const uint32_t ow[4] = {own.x, own.y, own.z, own.w};
-  float dot = 0.f;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    dot = fmaf(__uint_as_float(ow[e] << 16), G[2 * e], dot);
-    dot = fmaf(__uint_as_float(ow[e] & 0xffff0000u), G[2 * e + 1], dot);
-  }
-  return l.xs[i] * dot;
-}
-
-// dX0[b * S + i][c] = bf16(coef x_i G): one 16-B store
-__device__ __forceinline__ void ffm_store(const FfmK& p, const FfmLds& l, int64_t b, int t,
-                                          float coef, const float (&G)[8]) {
-  const int c = t / p.a.S, i = t - c * p.a.S;
-  const float s = coef * l.xs[i];
-  uint32_t o[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    o[e] = (uint32_t)f32_to_bf16(s * G[2 * e]) | ((uint32_t)f32_to_bf16(s * G[2 * e + 1]) << 16);
-  uint4* dst = reinterpret_cast<uint4*>((uint16_t*)p.a.dX0 + (b * p.a.S + i) * p.a.Dr);
-  dst[c] = make_uint4(o[0], o[1], o[2], o[3]);
+  ffm_store(p.a.dX0, b * p.a.S + i, p.a.Dr, c, coef * l.xs[i], G);
 }
 
 template <int K, int KEEP, bool kBwd>
@@ -140,24 +81,10 @@ __global__ void __launch_bounds__(256) ffm_kernel(const FfmK p) {
   for (int64_t b = blockIdx.x * (int64_t)W + wv; b < a.B; b += (int64_t)gridDim.x * W) {
     float lin = 0.f;
     if (lane < S) {
-      const int64_t pp = b * S + lane;
-      const float x = a.vals ? a.vals[pp] : 1.f;
-      const int64_t col = a.local_col ? (int64_t)a.local_col[pp] : pp;
-      const float w = in_range(col, a.w_cap) ? a.w_local[col] : 0.f;
-      int64_t r = col;
-      if (a.idx) r = in_range(r, a.idx_cap) ? a.idx[r] : -1;
-      const bool ok = in_range(r, a.rows_cap);  // unresolved key: zero row
-      const uint4* src = reinterpret_cast<const uint4*>((const uint16_t*)a.rows + (ok ? r : 0) * a.Dr);
-      uint4* dst = l.tile + lane * p.Q;
-      for (int c0 = 0; c0 < p.C; c0 += 4) {
-        uint4 q[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          q[u] = ok && c0 + u < p.C ? src[c0 + u] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (c0 + u < p.C) dst[c0 + u] = q[u];
-      }
+      float x, w;
+      bool ok;
+      const uint4* src = ffm_src(a, b * S + lane, x, w, ok);
+      ffm_stage(src, ok, l.tile + lane * p.Q, p.C);
       l.xs[lane] = x;
       lin = w * x;
     }
@@ -167,11 +94,11 @@ __global__ void __launch_bounds__(256) ffm_kernel(const FfmK p) {
 #pragma unroll
     for (int n = 0; n < KEEP; ++n) {
       const int t = lane + 64 * n;
-      if (t < p.items) part += ffm_item<K>(p, l, t, Gk[n]);
+      if (t < p.items) part += ffm_item<K>(l, S, p.Q, a.F, t, Gk[n]);
     }
     for (int t = lane + 64 * KEEP; t < p.items; t += 64) {
       float G[8];
-      part += ffm_item<K>(p, l, t, G);
+      part += ffm_item<K>(l, S, p.Q, a.F, t, G);
     }
     const float m = wave_allsum(lin + 0.5f * part);
     if (!kBwd) {
@@ -185,35 +112,17 @@ __global__ void __launch_bounds__(256) ffm_kernel(const FfmK p) {
 #pragma unroll
     for (int n = 0; n < KEEP; ++n) {
       const int t = lane + 64 * n;
-      if (t < p.items) ffm_store(p, l, b, t, coef, Gk[n]);
+      if (t < p.items) ffm_store_item(p, l, b, t, coef, Gk[n]);
     }
     for (int t = lane + 64 * KEEP; t < p.items; t += 64) {
       float G[8];
-      ffm_item<K>(p, l, t, G);
-      ffm_store(p, l, b, t, coef, G);
+      ffm_item<K>(l, S, p.Q, a.F, t, G);
+      ffm_store_item(p, l, b, t, coef, G);
     }
-    if (lane == 0) {
-      a.coef[b] = coef;
-      loss_acc += ym > 20.f ? expf(-ym) : (ym < -20.f ? -ym : log1pf(expf(-ym)));
-      corr_acc += ((y > 0.f) == (m > 0.f)) ? 1.0 : 0.0;
-      cnt += 1.0;
-      if (a.hist) {
-        const float pr = 1.f / (1.f + expf(-m));
-        const float pb = pr == pr ? fminf(fmaxf(pr * a.nbins, 0.f), (float)(a.nbins - 1)) : 0.f;
-        atomicAdd(&a.hist[(y > 0.f ? a.nbins : 0) + (int)pb], 1u);
-      }
-    }
+    if (lane == 0) ffm_row_done(a, b, y, m, coef, loss_acc, corr_acc, cnt);
     wave_lds_sync();
   }
-  if (kBwd && a.metrics) {  // per-wave DPP sums, lane 63 adds (no barriers)
-    const double ls = wave_sum_dpp(loss_acc), c = wave_sum_dpp(corr_acc), n = wave_sum_dpp(cnt);
-    if (lane == 63 && n > 0) {
-      double* mt = acc_stripe(a.metrics, a.acc_stripes);
-      atomicAdd(&mt[0], ls);
-      atomicAdd(&mt[1], c);
-      atomicAdd(&mt[2], n);
-    }
-  }
+  if (kBwd && a.metrics) ffm_metrics(a, loss_acc, corr_acc, cnt);
 }
 
 // G of a lane's first kKeep items stays in registers between the passes. The compiler

@@ -17,7 +17,16 @@ two positions. The step is ``FMTrainer``'s fixed-width step with ``ffm_fwd_bwd``
 one wavefront per example on an LDS tile of its rows) in place of ``fm_fwd_bwd_gather``:
 localise -> pull rows + w -> forward / backward -> per-key reduction of dX0 + L2 -> AdaGrad
 rows; wide gradient by the sparse-LR segmented reduction. G > 1 pulls / pushes packed
-``[v | w]`` records (``EmbeddingPS``). CSR rows and a fused table-probe scorer are not here.
+``[v | w]`` records (``EmbeddingPS``).
+
+``step(..., row_ptr=, fields=)`` / ``predict(..., row_ptr=, fields=)`` take CSR minibatches with
+a field id per occurrence (libffm's ``field:index:value`` rows; the device text parsers' CSR
+arrays with one slot id per feature): rows of any width, fields missing, repeated, in any
+order. ``fields`` [nnz] int32 then replaces the position -> field map; a field outside [0, F)
+keeps the occurrence's linear term and takes it out of every pair. The step is the same
+sequence with ``ffm_csr`` (ffm_csr.hip) as its forward / backward: rows of up to ``cfg.slots``
+positions run on the per-wave LDS tile with field lists built in the wave, wider rows on a
+second launch that reads partners from global memory. A fused table-probe scorer is not here.
 """
 from __future__ import annotations
 
@@ -116,15 +125,21 @@ class FFMTrainer(EmbeddingPS):
             self.dX0 = torch.empty(self.max_nnz, Dr, dtype=torch.bfloat16, device=dev)
             self.dE = torch.empty(self.max_nnz, Dr, dtype=torch.float32, device=dev)
             self.rows_u = torch.empty(self.max_nnz, Dr, dtype=torch.bfloat16, device=dev)
+            self.row_of = None  # [max_nnz] int32, on the first CSR step
         self.step_count = 0
         self.examples = 0
         self.t0 = time.time()
 
     # ------------------------------------------------------------------ step
     def step(self, keys: torch.Tensor, labels: torch.Tensor, vals: torch.Tensor | None = None,
-             loc=None):
+             loc=None, row_ptr: torch.Tensor | None = None, fields: torch.Tensor | None = None):
         """One minibatch: ``keys`` [B*S] raw feature ids (row-major, S per example),
-        ``labels`` [B] in {-1, +1} (or {0, 1}), optional feature values ``vals`` [B*S]."""
+        ``labels`` [B] in {-1, +1} (or {0, 1}), optional feature values ``vals`` [B*S]. With
+        ``row_ptr`` [B + 1] (int64) and ``fields`` [nnz] (int32, on the trainer's device) the
+        rows have any width and every occurrence names its own field (``cfg.fields`` is not
+        used): row b holds keys[row_ptr[b]:row_ptr[b + 1]]."""
+        if row_ptr is not None or fields is not None:
+            return self._step_csr(keys, labels, vals, loc, row_ptr, fields)
         cfg = self.cfg
         S, Dr = cfg.slots, self.Dr
         B = labels.numel()
@@ -211,7 +226,11 @@ class FFMTrainer(EmbeddingPS):
         """ffm_fwd_bwd in PyTorch: the CPU route, and in ``dtype=torch.float64`` the
         reference the kernel is tested against."""
         m, c, dX = self._fwd_bwd_math(X0, vals, B, S, local_col, w_wide, labels, dtype)
-        y = torch.where(labels[:B] > 0, 1.0, -1.0).to(dtype)
+        return self._account(m, c, dX, labels, B)
+
+    def _account(self, m, c, dX, labels, B):
+        """What the kernels write beside dX0: coef, loss / accuracy / count, the AUC bins."""
+        y = torch.where(labels[:B] > 0, 1.0, -1.0).to(m.dtype)
         self.coef[:B] = c
         self.metrics[0] += torch.nn.functional.softplus(-y * m).double().sum()
         self.metrics[1] += ((y > 0) == (m > 0)).double().sum()
@@ -222,18 +241,147 @@ class FFMTrainer(EmbeddingPS):
             self.hist.dtype)
         return dX.to(torch.bfloat16)
 
+    # ------------------------------------------------------------------ CSR rows
+    def _check_csr(self, nnz: int, B: int, row_ptr, fields, vals) -> None:
+        """Everything a CSR minibatch can get wrong, before anything is launched (shapes and
+        dtypes only: the widths and the field ids are device data)."""
+        if row_ptr is None or fields is None:
+            raise ValueError("CSR rows need both row_ptr [B + 1] and fields [nnz]")
+        if row_ptr.numel() != B + 1:
+            raise ValueError(f"row_ptr has {row_ptr.numel()} entries for {B} rows, not {B + 1}")
+        if row_ptr.dtype != torch.int64:
+            raise ValueError("row_ptr must be int64")
+        if fields.numel() != nnz:
+            raise ValueError(f"expected {nnz} fields, got {fields.numel()}")
+        if fields.dtype != torch.int32:
+            raise ValueError("fields must be int32")
+        if fields.device.type != self.device.type:
+            raise ValueError(f"fields must be on the trainer's device ({self.device})")
+        if vals is not None and vals.numel() != nnz:
+            raise ValueError(f"expected {nnz} values, got {vals.numel()}")
+
+    def _step_csr(self, keys, labels, vals, loc, row_ptr, fields):
+        """step() on CSR rows with a field per occurrence: ``FMTrainer._step_csr``'s sequence
+        with ``ffm_csr`` (ffm_csr.hip) as its forward / backward; the kernel also writes the
+        row id of every occurrence for the wide gradient. ``cfg.slots`` is the row capacity
+        of the LDS tile, not a limit: wider rows take the kernel's global-memory path.
+        Nothing here reads device data on the host."""
+        cfg = self.cfg
+        Dr = self.Dr
+        B, nnz = labels.numel(), keys.numel()
+        self._check_csr(nnz, B, row_ptr, fields, vals)
+        if nnz > self.max_nnz:
+            raise ValueError(f"{nnz} keys in a minibatch, max_nnz is {self.max_nnz}")
+        if B > self.coef.numel():
+            raise ValueError(f"{B} rows in a minibatch, cfg.minibatch is {self.coef.numel()}")
+        loc = self.localizer(keys) if loc is None else loc
+        if self.G == 1:
+            if self.gpu:
+                slot, w_wide = self.shard.resolve(loc.uniq, loc.n_uniq, self.slot_buf, self.w_buf)
+            else:
+                slot, w_wide = self.shard.resolve(loc.uniq[:loc.num_unique()])
+            rows_src, rows_idx = self.shard.rows, slot
+            if self.gpu and cfg.compact_rows:
+                hipops().emb_gather_rows(slot, self.shard.rows, self.rows_u, loc.n_uniq)
+                rows_src, rows_idx = self.rows_u, None
+            push = ("local", slot)
+        else:
+            rows_u, w_wide, push = self._pull(loc)
+            rows_src, rows_idx = rows_u, None
+        if self.gpu:
+            if self.row_of is None:
+                self.row_of = torch.empty(self.max_nnz, dtype=torch.int32, device=self.device)
+            dX0, row_of = self.dX0[:nnz], self.row_of[:nnz]
+            hipops().ffm_csr(row_ptr, fields, nnz, rows_src, rows_idx, vals, B, cfg.slots, self.F,
+                             cfg.k, loc.local_col, w_wide, labels, self.coef, dX0, row_of,
+                             self.metrics, self.hist, AUC_BINS)
+            dE = E.grad_reduce(loc, dX0, Dr, nnz, out=self.dE)
+            l2_cap = nnz if rows_idx is not None else min(nnz, rows_src.shape[0])
+            hipops().fm_l2(dE, rows_src, rows_idx, loc.n_uniq, l2_cap, cfg.lambda_v)
+        else:
+            X0 = E.expand(loc.local_col, nnz, rows_src, idx=rows_idx)
+            row_of = torch.repeat_interleave(torch.arange(B), row_ptr[1:] - row_ptr[:-1])
+            dX0 = self._fwd_bwd_torch_csr(X0, vals, row_of, fields, loc.local_col, w_wide, labels)
+            U = loc.num_unique()
+            dE = E.grad_reduce(loc, dX0, Dr, U)
+            v = (rows_src[rows_idx[:U]] if rows_idx is not None else rows_src[:U]).float()
+            dE += cfg.lambda_v * v
+        g_wide, _ = linear_backward(loc, self.coef[:B], B=B, rows=row_of, vals=vals)
+        self._push(loc, push, dE, g_wide)
+        auc_from_hist(self.hist, self.metrics, self.step_dev)
+        self.step_count += 1
+        self.examples += B
+
+    def _pairs_torch_csr(self, X0, x, row_of, fld, B, dtype):
+        """``_pairs_torch`` on CSR rows: the rows are gathered into a padded [B, W] block (W
+        the widest row) where an absent position, or an occurrence whose field is outside
+        [0, F), has x = 0 and so enters no pair. Returns G [nnz, F, k] (zero for such an
+        occurrence), the pair part of the margin [B] and the masked x [nnz]."""
+        F, k = self.F, self.cfg.k
+        nnz, dev = row_of.numel(), X0.device
+        r = row_of.long()
+        width = torch.bincount(r, minlength=B)
+        W = max(int(width.max()) if nnz else 0, 1)
+        col = torch.arange(nnz, device=dev) - (torch.cumsum(width, 0) - width)[r]
+        f = fld[:nnz].long()
+        ok = (f >= 0) & (f < F)
+        x = x * ok
+        Vp = torch.zeros(B, W, F, k, dtype=dtype, device=dev)
+        Vp[r, col] = X0[:nnz, :F * k].to(dtype).reshape(nnz, F, k)
+        xp = torch.zeros(B, W, dtype=dtype, device=dev)
+        xp[r, col] = x
+        fp = torch.zeros(B, W, dtype=torch.long, device=dev)
+        fp[r, col] = torch.where(ok, f, 0)
+        bi = torch.arange(B, device=dev)[:, None, None]
+        ji = torch.arange(W, device=dev)[None, None, :]
+        P = Vp[bi, ji, fp[:, :, None]]  # P[b, i, j] = v_{j, f_i}
+        off = 1.0 - torch.eye(W, dtype=dtype, device=dev)
+        P = P * (xp[:, None, :] * off)[..., None]
+        G = torch.zeros(B, W, F, k, dtype=dtype, device=dev).scatter_add_(
+            2, fp[:, None, :, None].expand(B, W, W, k), P)
+        pair = 0.5 * (xp * (Vp * G).sum((2, 3))).sum(1)
+        return G[r, col] * ok[:, None, None], pair, x
+
+    def _fwd_bwd_math_csr(self, X0, vals, row_of, fld, local_col, w_wide, labels,
+                          dtype=torch.float32):
+        """(margin [B], coef [B], dX0 [nnz, Dr]) in ``dtype``, nothing rounded to bf16."""
+        nnz, B, dev = row_of.numel(), labels.numel(), X0.device
+        x = vals[:nnz].to(dtype) if vals is not None else torch.ones(nnz, dtype=dtype, device=dev)
+        G, pair, xq = self._pairs_torch_csr(X0, x, row_of, fld, B, dtype)
+        m = torch.zeros(B, dtype=dtype, device=dev).index_add_(
+            0, row_of.long(), w_wide.to(dtype)[local_col[:nnz].long()] * x) + pair
+        y = torch.where(labels > 0, 1.0, -1.0).to(dtype)
+        c = -y * torch.sigmoid(-y * m)
+        dX = torch.zeros(nnz, self.Dr, dtype=dtype, device=dev)
+        dX[:, :self.F * self.cfg.k] = ((c[row_of.long()] * xq)[:, None, None] * G).reshape(nnz, -1)
+        return m, c, dX
+
+    def _fwd_bwd_torch_csr(self, X0, vals, row_of, fld, local_col, w_wide, labels,
+                           dtype=torch.float32):
+        """ffm_csr in PyTorch: the CPU route, and in ``dtype=torch.float64`` the reference
+        the kernels are tested against. ``row_of`` [nnz] is the row of every occurrence
+        (rows in order), ``fld`` [nnz] its field."""
+        m, c, dX = self._fwd_bwd_math_csr(X0, vals, row_of, fld, local_col, w_wide, labels, dtype)
+        return self._account(m, c, dX, labels, labels.numel())
+
     # ------------------------------------------------------------------ eval
-    def predict(self, keys: torch.Tensor, B: int, vals: torch.Tensor | None = None) -> torch.Tensor:
+    def predict(self, keys: torch.Tensor, B: int, vals: torch.Tensor | None = None,
+                row_ptr: torch.Tensor | None = None,
+                fields: torch.Tensor | None = None) -> torch.Tensor:
         """Margins of B examples (no update, no insert; unseen keys contribute 0). G == 1.
-        A GPU trainer scores with the forward-only kernel (``ffm_margins``), slots and
-        wide weights per occurrence."""
+        Rows of ``cfg.slots`` keys, or CSR rows with ``row_ptr`` [B + 1] and ``fields``
+        [nnz] as ``step``. A GPU trainer scores with the forward-only kernels
+        (``ffm_margins`` / ``ffm_csr_margins``), slots and wide weights per occurrence."""
         if self.G != 1:
             raise NotImplementedError("predict() reads the local shard (G == 1)")
         from ..ops.keymix import mix
 
         S = self.cfg.slots
         nnz = keys.numel()
-        if nnz != B * S:
+        csr = row_ptr is not None or fields is not None
+        if csr:
+            self._check_csr(nnz, B, row_ptr, fields, vals)
+        elif nnz != B * S:
             raise ValueError(f"expected {B * S} keys, got {nnz}")
         mk = mix(keys.to(self.device), self.bits)
         slot, w = self.shard.table.resolve(mk, insert=False)
@@ -241,12 +389,21 @@ class FFMTrainer(EmbeddingPS):
         w = torch.where(ok, w, torch.zeros_like(w))
         if self.gpu:
             margins = torch.empty(B, dtype=torch.float32, device=self.device)
-            hipops().ffm_margins(self.shard.rows, slot, vals, B, S, self.fields, self.F,
-                                 self.cfg.k, None, w, margins)
+            if csr:
+                hipops().ffm_csr_margins(row_ptr, fields, nnz, self.shard.rows, slot, vals, B, S,
+                                         self.F, self.cfg.k, None, w, margins)
+            else:
+                hipops().ffm_margins(self.shard.rows, slot, vals, B, S, self.fields, self.F,
+                                     self.cfg.k, None, w, margins)
             return margins
         X0 = torch.zeros(nnz, self.Dr, device=self.device)
         X0[ok] = self.shard.rows[slot[ok]].float()
-        x = (vals.float() if vals is not None else torch.ones(nnz)).reshape(B, S)
+        x = vals.float() if vals is not None else torch.ones(nnz)
+        if csr:
+            r = torch.repeat_interleave(torch.arange(B), row_ptr[1:] - row_ptr[:-1])
+            pair = self._pairs_torch_csr(X0, x, r, fields, B, torch.float32)[1]
+            return torch.zeros(B).index_add_(0, r, w * x) + pair
+        x = x.reshape(B, S)
         return (w.reshape(B, S) * x).sum(1) + self._pairs_torch(X0, x, torch.float32)[1]
 
     progress = FMTrainer.progress
