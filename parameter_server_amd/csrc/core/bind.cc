@@ -78,14 +78,14 @@ PYBIND11_MODULE(_pscore, m) {
     kv_set(P<Slot>(slots), P<const int64_t>(idx), n, w ? P<const float>(w) : nullptr,
            z ? P<const float>(z) : nullptr, nn ? P<const float>(nn) : nullptr);
   });
-  m.def("kv_update", [](uintptr_t slots, uintptr_t idx, uintptr_t grad, int64_t n, int algo,
-                        int lr_type, double alpha, double beta, double l1, double l2,
+  m.def("kv_update", [](uintptr_t slots, int64_t cap, uintptr_t idx, uintptr_t grad, int64_t n,
+                        int algo, int lr_type, double alpha, double beta, double l1, double l2,
                         double grad_scale, double max_delta, uintptr_t stats) {
     if (!(alpha > 0)) throw std::invalid_argument("learning rate alpha must be > 0");
     UpdateParams p{algo, lr_type, (float)alpha, (float)beta, (float)l1, (float)l2,
                    (float)grad_scale, (float)max_delta};
     py::gil_scoped_release rel;
-    kv_update(P<Slot>(slots), P<const int64_t>(idx), P<const float>(grad), n, p,
+    kv_update(P<Slot>(slots), cap, P<const int64_t>(idx), P<const float>(grad), n, p,
               stats ? P<double>(stats) : nullptr);
   });
   m.def("kv_census", [](uintptr_t slots, int64_t cap) {

@@ -159,12 +159,12 @@ static float prox(float zz, float eta, float l1, float l2) {
   return (zz > 0.f ? zz - leta : zz + leta) / (1.f + l2 * eta);
 }
 
-void kv_update(Slot* slots, const int64_t* idx, const float* grad, int64_t n,
+void kv_update(Slot* slots, int64_t cap, const int64_t* idx, const float* grad, int64_t n,
                const UpdateParams& p, double* stats) {
   double dnnz = 0, wsum = 0, dsum = 0;
   for (int64_t i = 0; i < n; ++i) {
     const int64_t si = idx[i];
-    if (si < 0) continue;
+    if (si < 0 || si >= cap) continue;  // absent or stale index (kv_table.hip in_range)
     const float g = grad[i] * p.grad_scale;
     if (g != g) continue;
     Slot& s = slots[si];

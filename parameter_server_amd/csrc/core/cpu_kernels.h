@@ -44,7 +44,7 @@ int64_t kv_rehash(const Slot* old_slots, int64_t old_cap, Slot* slots, int64_t c
 void kv_gather(const Slot* slots, const int64_t* idx, int64_t n, float* out, int field);
 void kv_set(Slot* slots, const int64_t* idx, int64_t n, const float* w, const float* z,
             const float* nn);
-void kv_update(Slot* slots, const int64_t* idx, const float* grad, int64_t n,
+void kv_update(Slot* slots, int64_t cap, const int64_t* idx, const float* grad, int64_t n,
                const UpdateParams& p, double* stats);
 void kv_census(const Slot* slots, int64_t cap, int64_t* occ, int64_t* nnz);
 

@@ -197,7 +197,8 @@ __device__ __forceinline__ void accumulate_one(Slot* __restrict__ slots, int64_t
   bool first = false;
   if (valid && in_range(si, cap) && g == g) {  // NaN mark = filtered entry
     atomicAdd(&slots[si].acc, g);
-    first = atomicOr(&slots[si].flags, 1u) == 0u;
+    // (bit 0 alone: a slot with a published non-zero init carries bit 1, kSlotInit)
+    first = (atomicOr(&slots[si].flags, 1u) & 1u) == 0u;
   }
   const uint64_t m = __ballot(first);
   if (!m) return;

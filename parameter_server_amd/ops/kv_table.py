@@ -141,7 +141,7 @@ class KVTable:
             hipops().kv_update(self.slots, slot_idx, grad.contiguous(), n_dev, *rule.args(), stats)
         else:
             assert n_dev is None
-            core().kv_update(ptr(self.slots), ptr(slot_idx), ptr(grad.contiguous()),
+            core().kv_update(ptr(self.slots), self.capacity, ptr(slot_idx), ptr(grad.contiguous()),
                              slot_idx.numel(), *rule.args(), ptr(stats))
 
     # ------------------------------------------------------------- inspection

@@ -255,10 +255,19 @@ def test_bucketed_auc_close_to_exact():
     hist = torch.zeros(2 * AUC_BINS, dtype=torch.int32, device=DEV)
     p = torch.sigmoid(s)
     b = torch.clamp((p * AUC_BINS).long(), 0, AUC_BINS - 1) + torch.where(y > 0, AUC_BINS, 0)
-    hist += torch.bincount(b, minlength=2 * AUC_BINS).to(torch.int32).to(DEV)
+    counts = torch.bincount(b, minlength=2 * AUC_BINS)
+    hist += counts.to(torch.int32).to(DEV)
     m = torch.zeros(8, dtype=torch.float64, device=DEV)
     auc_from_hist(hist, m)
     assert abs(float(m[3]) - exact_auc(s, y)) < 2e-3
+    # and the device value IS the integer AUC of its own histogram (in-bin ties count half):
+    # 2 * area is exact in u64, then one multiply and one divide in double
+    below = a2 = 0
+    for nb, pb in zip(counts[:AUC_BINS].tolist(), counts[AUC_BINS:].tolist()):
+        a2 += pb * (2 * below + nb)
+        below += nb
+    want = 0.5 * a2 / (int(counts[AUC_BINS:].sum()) * below)
+    assert abs(float(m[3]) - want) <= 1e-15 * want
     assert int(hist.sum().item()) == 0
 
 

@@ -9,20 +9,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _rows(G, C, n_per, span, lo, seed, nan_frac=0.0, dup_pool=None, kw=1):
-    """Exchange rows [nkeys, ngrads, -, -, keys (u32, or u64 for kw = 2), grads]: row s holds
-    n_per[s] sorted distinct keys in [lo, lo + span), many shared across rows."""
-    g = torch.Generator().manual_seed(seed)
+def pack_rows(rows, C, kw=1):
+    """Exchange rows [nkeys, ngrads, -, -, keys (u32, or u64 for kw = 2), grads] of capacity
+    C from a list of (sorted int64 keys, float32 grads) per source: (recv int32, stride H)."""
     H = (4 + C * kw + C + 3) // 4 * 4
-    recv = torch.zeros(G * H, dtype=torch.int32)
-    pool = dup_pool if dup_pool is not None else torch.randperm(span, generator=g)[: 3 * max(n_per)]
-    for s in range(G):
-        n = n_per[s]
-        pick = pool[torch.randperm(pool.numel(), generator=g)[:n]]
-        keys = torch.sort(pick + lo).values
-        grads = torch.randn(n, generator=g)
-        if nan_frac:
-            grads[torch.rand(n, generator=g) < nan_frac] = float("nan")
+    recv = torch.zeros(len(rows) * H, dtype=torch.int32)
+    for s, (keys, grads) in enumerate(rows):
+        n = keys.numel()
         row = recv[s * H:(s + 1) * H]
         row[0] = n
         row[1] = n
@@ -32,6 +25,54 @@ def _rows(G, C, n_per, span, lo, seed, nan_frac=0.0, dup_pool=None, kw=1):
             row[4:4 + n] = keys.to(torch.int64).to(torch.int32)  # u32 bit pattern
         row[4 + C * kw:4 + C * kw + n] = grads.view(torch.int32)
     return recv, H
+
+
+def _rows(G, C, n_per, span, lo, seed, nan_frac=0.0, dup_pool=None, kw=1):
+    """Row s holds n_per[s] sorted distinct keys in [lo, lo + span), many shared across rows."""
+    g = torch.Generator().manual_seed(seed)
+    pool = dup_pool if dup_pool is not None else torch.randperm(span, generator=g)[: 3 * max(n_per)]
+    rows = []
+    for s in range(G):
+        n = n_per[s]
+        pick = pool[torch.randperm(pool.numel(), generator=g)[:n]]
+        keys = torch.sort(pick + lo).values
+        grads = torch.randn(n, generator=g)
+        if nan_frac:
+            grads[torch.rand(n, generator=g) < nan_frac] = float("nan")
+        rows.append((keys, grads))
+    return pack_rows(rows, C, kw)
+
+
+def resolve_rows(tb, recv, H, C, G, lgP, kw=1):
+    """kv_resolve_rows of G received rows into table ``tb`` (inserting): (slot, keys, bnd),
+    what the two apply kernels take; bnd = the per-row bounds of the 2^lgP key partitions."""
+    from parameter_server_amd.ops.native import hipops
+
+    dev = recv.device
+    slot = torch.full((G * C,), -1, dtype=torch.int64, device=dev)
+    w = torch.zeros(G * C, dtype=torch.float32, device=dev)
+    keys = torch.zeros(G * C, dtype=torch.int64, device=dev)
+    bnd = torch.full((G * ((1 << lgP) + 1),), -5, dtype=torch.int32, device=dev)
+    it, iv, isd, seed = tb.init.args()
+    hipops().kv_resolve_rows(tb.slots, recv, H, C, kw, slot, w, True, it, iv, isd, seed, tb._err,
+                             None, tb.home_base, tb.home_m, keys, bnd, lgP)
+    return slot, keys, bnd
+
+
+def apply_rows(kernel, tb, recv, H, C, G, slot, keys, bnd, lgP, rule, stats, kw=1):
+    """One owner-side apply of all G rows with ``kernel`` (kv_update_rows: the chained-hash
+    pair; kv_apply_part: the key-range partitioned kernel)."""
+    from parameter_server_amd.ops.native import hipops
+    from parameter_server_amd.ops.kv_table import next_pow2
+
+    gsrc = recv.view(torch.float32)[4 + C * kw:]
+    if kernel == "kv_update_rows":
+        link = torch.empty(next_pow2(2 * G * C), dtype=torch.int64, device=recv.device)
+        nxt = torch.empty(G * C, dtype=torch.int32, device=recv.device)
+        hipops().kv_update_rows(tb.slots, slot, gsrc, H, recv, H, C, link, nxt, *rule.args(), stats)
+    else:
+        hipops().kv_apply_part(tb.slots, slot, keys, gsrc, H, recv, H, C, bnd, lgP, *rule.args(),
+                               stats, 0, kw)
 
 
 @pytest.mark.parametrize("G,C,lgP,nan,kw", [
@@ -44,8 +85,7 @@ def _rows(G, C, n_per, span, lo, seed, nan_frac=0.0, dup_pool=None, kw=1):
     pytest.param(3, 2048, 3, 0.0, 2, id="3-2048-3-0.0-kw2"),
     pytest.param(8, 4096, 6, 0.1, 2, id="8-4096-6-0.1-kw2")])
 def test_partitioned_apply_matches_chained(G, C, lgP, nan, kw):
-    from parameter_server_amd.ops.native import hipops
-    from parameter_server_amd.ops.kv_table import KVTable, UpdateRule, next_pow2
+    from parameter_server_amd.ops.kv_table import KVTable, UpdateRule
 
     dev = torch.device("cuda")
     lo, span = (1 << 20) if kw == 1 else (1 << 40), 1 << 22
@@ -54,16 +94,9 @@ def test_partitioned_apply_matches_chained(G, C, lgP, nan, kw):
     recv = recv.to(dev)
     tabs = [KVTable(1 << 16, dev, key_range=(lo, lo + span)) for _ in range(2)]
     rule = UpdateRule(algo="ftrl", alpha=0.1, beta=1.0, l1=0.5, l2=0.1)
-    hh = hipops()
     P = 1 << lgP
-    slot = torch.full((G * C,), -1, dtype=torch.int64, device=dev)
-    w = torch.zeros(G * C, dtype=torch.float32, device=dev)
-    keys = torch.zeros(G * C, dtype=torch.int64, device=dev)
-    bnd = torch.full((G * (P + 1),), -5, dtype=torch.int32, device=dev)
     tb = tabs[0]
-    it, iv, isd, seed = tb.init.args()
-    hh.kv_resolve_rows(tb.slots, recv, H, C, kw, slot, w, True, it, iv, isd, seed, tb._err,
-                       None, tb.home_base, tb.home_m, keys, bnd, lgP)
+    slot, keys, bnd = resolve_rows(tb, recv, H, C, G, lgP, kw)
     tabs[1].slots.copy_(tb.slots)  # same placement (insert races may differ per table)
     torch.cuda.synchronize()
     # bounds: row s, partition q -> number of its keys with part(key) < q
@@ -81,13 +114,9 @@ def test_partitioned_apply_matches_chained(G, C, lgP, nan, kw):
                                sent.to(torch.int64) & 0xFFFFFFFF)
     # a second push round on top of the first exercises non-zero optimizer state
     for _ in range(2):
-        gsrc = recv.view(torch.float32)[4 + C * kw:]
         st = [torch.zeros(3, dtype=torch.float64, device=dev) for _ in range(2)]
-        link = torch.empty(next_pow2(2 * G * C), dtype=torch.int64, device=dev)
-        nxt = torch.empty(G * C, dtype=torch.int32, device=dev)
-        hh.kv_update_rows(tabs[0].slots, slot, gsrc, H, recv, H, C, link, nxt, *rule.args(), st[0])
-        hh.kv_apply_part(tabs[1].slots, slot, keys, gsrc, H, recv, H, C, bnd, lgP, *rule.args(),
-                         st[1], 0, kw)
+        for kernel, tab, stats in zip(("kv_update_rows", "kv_apply_part"), tabs, st):
+            apply_rows(kernel, tab, recv, H, C, G, slot, keys, bnd, lgP, rule, stats, kw)
         torch.cuda.synchronize()
         assert torch.equal(tabs[0].slots, tabs[1].slots)
         torch.testing.assert_close(st[0], st[1], rtol=1e-9, atol=1e-9)

@@ -52,12 +52,13 @@ def _key_weights(keys):
 class _Case:
     """One localisation of a shape in one layout: ``cols`` maps every occurrence to the
     index of its weight (unique id for "tp", tile entry for "tpf"), ``live`` marks the
-    gradient slots the kernel writes, ``run(labels, loss)`` launches the fused kernel."""
+    gradient slots the kernel writes, ``run(labels, loss)`` launches the fused kernel.
+    ``batch``: the (keys, labels, real labels, vals) to use instead of ``_batch``'s."""
 
-    def __init__(self, layout, B, width, with_vals):
+    def __init__(self, layout, B, width, with_vals, batch=None):
         self.B, self.width = B, width
-        keys, self.labels, self.real, self.vals = _batch(B, width, with_vals)
-        n = keys.numel()
+        keys, self.labels, self.real, self.vals = batch or _batch(B, width, with_vals)
+        self.n = n = keys.numel()
         i = torch.arange(n, device=DEV)
         if layout == "tp":
             self.loc = loc = Localizer(n, 30, DEV, mode="tp", lazy_cols=True)(keys)
@@ -99,6 +100,24 @@ class _Case:
             grad = f.psum
         torch.cuda.synchronize()
         return coef, grad, accum_total(metrics).cpu(), hist.view(-1, 2 * AUC_BINS).sum(0).cpu()
+
+    def run_csr(self, labels, loss, row_ptr, rows):
+        """The same localisation through the variable-width kernel (tp_fwd_bwd_csr_kernel):
+        rows of any width, empty ones included, given by ``row_ptr`` [B + 1] int64 and the
+        row of every occurrence ``rows`` [n] int32; the tile partials are left unreduced."""
+        B = row_ptr.numel() - 1
+        assert rows.numel() == self.n == int(row_ptr[-1]) and labels.numel() == B
+        coef = torch.empty(B, device=DEV)
+        metrics = new_accum(DEV)
+        hist = torch.zeros(HIST_STRIPES * 2 * AUC_BINS, dtype=torch.int32, device=DEV)
+        t = self.loc.tile if self.layout == "tp" else self.loc
+        hipops().tp_fwd_bwd_csr(t.rep, t.dcnt, t.ent_uid if self.layout == "tp" else None, self.n,
+                                row_ptr, rows, self.vals, self.w, labels, B, loss_id(loss), coef,
+                                metrics, hist, AUC_BINS, self.partials, None, None, None, None,
+                                False)
+        torch.cuda.synchronize()
+        return (coef, self.partials, accum_total(metrics).cpu(),
+                hist.view(-1, 2 * AUC_BINS).sum(0).cpu())
 
     def reference(self, labels, loss):
         """Plain torch (tests/test_tp_fused_gpu.py _reference) + the AUC bins."""

@@ -102,8 +102,14 @@ def test_grad_reduce_fused_wide_gradient(D, B, S, hot):
     assert torch.equal(gw2[:U], gw[:U])
 
 
-@pytest.mark.parametrize("algo", ["ftrl", "adagrad", "sgd"])
-def test_fused_row_and_wide_update_is_the_two_pass_update(algo):
+@pytest.mark.parametrize("algo,grad_scale,max_delta", [
+    pytest.param("ftrl", 1.0, 0.0, id="ftrl"), pytest.param("adagrad", 1.0, 0.0, id="adagrad"),
+    pytest.param("sgd", 1.0, 0.0, id="sgd"),
+    # scaled gradients and a clip that binds (every slot starts at w = 0.25 and one FTRL /
+    # AdaGrad / SGD step from there moves most weights further than 0.002); kv_update
+    # itself is held to the float64 rule in test_update_rule_gpu.py
+    ("ftrl", 0.3, 0.002), ("adagrad", 0.3, 0.002), ("sgd", 0.3, 0.002)])
+def test_fused_row_and_wide_update_is_the_two_pass_update(algo, grad_scale, max_delta):
     """emb_update with the wide slots (one pass) = emb_update then kv_update: rows,
     AdaGrad accumulators and slots bitwise, stats to fp64 rounding; NaN-marked wide
     gradients skip only the slot."""
@@ -113,7 +119,9 @@ def test_fused_row_and_wide_update_is_the_two_pass_update(algo):
     H = hipops()
     D, cap, n = 128, 1 << 14, 5000
     g = torch.Generator().manual_seed(7)
-    keys = torch.randperm(1 << 30, generator=g)[:n].to(torch.int64)
+    # n distinct keys below 2^30 in random order (a whole randperm(2^30) took 40 s)
+    keys = torch.unique(torch.randint(0, 1 << 30, (2 * n,), generator=g))
+    keys = keys[torch.randperm(keys.numel(), generator=g)[:n]]
     dE = torch.randn(n, D, generator=g).cuda()
     gw = torch.randn(n, generator=g).cuda()
     gw[::97] = float("nan")
@@ -126,7 +134,8 @@ def test_fused_row_and_wide_update_is_the_two_pass_update(algo):
         sh.rows.copy_(start[0])
         sh.acc.copy_(start[1])
         sh.table.slots.copy_(start[2])
-        rule = UpdateRule(algo=algo, alpha=0.05, beta=1.0, l1=0.01, l2=0.1)
+        rule = UpdateRule(algo=algo, alpha=0.05, beta=1.0, l1=0.01, l2=0.1,
+                          grad_scale=grad_scale, max_delta=max_delta)
         stats = torch.zeros(8, dtype=torch.float64, device="cuda")
         nd = torch.tensor([n - 3], dtype=torch.int32, device="cuda")
         if fused:
@@ -140,6 +149,11 @@ def test_fused_row_and_wide_update_is_the_two_pass_update(algo):
     (r0, a0, s0, st0), (r1, a1, s1, st1) = runs
     assert torch.equal(r0, r1) and torch.equal(a0, a1) and torch.equal(s0, s1)
     torch.testing.assert_close(st1[:3], st0[:3], rtol=1e-9, atol=1e-9)
+    if max_delta:  # the clip bound most slots: they moved by exactly max_delta (to rounding)
+        dw = (s1.view(torch.float32).view(-1, 8)[slot[:n - 3], 2] - 0.25).abs().cpu()
+        live = ~torch.isnan(gw[:n - 3]).cpu()
+        assert float(dw[live].max()) <= max_delta * (1 + 1e-4)
+        assert float((dw[live] > 0.99 * max_delta).float().mean()) > 0.5
 
 
 def test_head_colsum_adam_match_cpu():
