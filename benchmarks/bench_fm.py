@@ -114,6 +114,98 @@ def score_mode(args):
           flush=True)
 
 
+def ffm_score_mode(args):
+    """1 GPU: scoring held-out minibatches against a field-aware FM (k = 2, F = 39) with the
+    fused kernel (``FFMTrainer.scorer()``: ffm_predict.hip, margins only and labels +
+    accumulator) and with the composed route (``FFMTrainer.predict``: mix, resolve, where,
+    then ffm_margins or the two ffm_csr_margins launches), alternated window by window in this
+    one process on a table filled by a few training steps. Shapes: Criteo's B x 39 fixed rows;
+    the same rows as CSR with a quarter of the slots missing; CSR rows of 65..130 occurrences
+    (B / 4 rows), which the composed route serves from its global-memory kernel. Per route and
+    window: a host clock around the synchronised window, and device events around the same
+    launches (for the fused routes, one kernel per minibatch: the kernel's own time)."""
+    from parameter_server_amd.models.ffm import FFMConfig, FFMTrainer
+    from parameter_server_amd.ops.synthetic import criteo_batch
+
+    dev = torch.device("cuda", 0)
+    B, N, S = args.minibatch, int(args.num_features), 39
+    tr = FFMTrainer(FFMConfig(k=2, localize=args.localize, num_features=N, minibatch=B,
+                              table_capacity=min(args.table_slots, 1 << 24), seed=0), device=dev)
+    crit = [criteo_batch(B, seed=77, row0=i * B, num_features=N, device=dev)
+            for i in range(args.train_steps + 4)]
+    for i in range(args.train_steps):
+        tr.step(*crit[i])
+    sc = tr.scorer()
+    g = torch.Generator(device=dev).manual_seed(5)
+    slot_of = torch.arange(S, dtype=torch.int32, device=dev).repeat(B)
+    fixed, missing, wide = [], [], []
+    for k39, y in crit[args.train_steps:]:
+        fixed.append((k39, y, B, dict(width=S), {}))
+        keep = torch.rand(B * S, device=dev, generator=g) < 0.75
+        rp = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        rp[1:] = torch.cumsum(keep.view(B, S).sum(1), 0)
+        kw = dict(row_ptr=rp, fields=slot_of[keep])
+        missing.append((k39[keep], y, B, kw, kw))
+        Bw = B // 4
+        rp = torch.zeros(Bw + 1, dtype=torch.int64, device=dev)
+        rp[1:] = torch.cumsum(torch.randint(65, 131, (Bw,), device=dev, generator=g), 0)
+        nnz = int(rp[-1])
+        pick = torch.randint(0, B * S, (nnz,), device=dev, generator=g)
+        kw = dict(row_ptr=rp, fields=slot_of[pick])  # a held-out key in its own slot's field
+        wide.append((k39[pick], y[:Bw].contiguous(), Bw, kw, kw))
+
+    def measure(tag, held, n):
+        """held: (keys, labels, rows, the scorer's keywords, predict's keywords)"""
+        routes = {"fused_margins": lambda b: sc.predict(b[0], **b[3]),
+                  "fused_labels_acc": lambda b: sc.score(b[0], b[1], margins=False, **b[3]),
+                  "composed_predict": lambda b: tr.predict(b[0], b[2], **b[4])}
+        a, c = routes["fused_margins"](held[0]), routes["composed_predict"](held[0])
+        print(f"{tag}: max |fused - composed| margin = {float((a - c).abs().max()):.3g}, "
+              f"max |margin| = {float(c.abs().max()):.3g}", flush=True)
+        host, devt = {r: [] for r in routes}, {r: [] for r in routes}
+        for fn in routes.values():
+            for i in range(args.warmup):
+                fn(held[i % len(held)])
+        for r in range(max(args.repeats, 5)):
+            for name, fn in routes.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e0.record()
+                for i in range(n):
+                    fn(held[i % len(held)])
+                e1.record()
+                torch.cuda.synchronize()
+                host[name].append((time.perf_counter() - t0) / n * 1e3)
+                devt[name].append(e0.elapsed_time(e1) / n)
+            print(f"{tag} window {r}: " + "  ".join(
+                f"{k} {host[k][-1]:.4f} ms (events {devt[k][-1]:.4f})" for k in routes), flush=True)
+        med = lambda d: {k: sorted(v)[len(v) // 2] for k, v in d.items()}
+        span = lambda d: {k: [min(v), max(v)] for k, v in d.items()}
+        mh, md = med(host), med(devt)
+        return {"rows": held[0][2], "nnz": held[0][0].numel(), "minibatches_per_window": n,
+                "median_ms": mh, "min_max_ms": span(host), "median_event_ms": md,
+                "min_max_event_ms": span(devt),
+                "composed_over_fused_margins": mh["composed_predict"] / mh["fused_margins"],
+                "composed_over_fused_margins_events":
+                    md["composed_predict"] / md["fused_margins"]}
+
+    n = max(args.steps, 100)
+    res = {"criteo_fixed_39": measure("criteo fixed", fixed, n),
+           "criteo_csr_quarter_missing": measure("criteo csr missing", missing, n),
+           "csr_wide_65_130": measure("csr wide", wide, max(n // 5, 20))}
+    occ, _ = tr.shard.table.census()
+    print(json.dumps({
+        "metric": "FFM scoring time per minibatch, fused kernel (FFMScorer) vs "
+                  "FFMTrainer.predict, 1 GPU, F = 39, k = 2, rows of 80 columns",
+        "unit": "ms/minibatch (median of windows)", "windows": max(args.repeats, 5),
+        "minibatch": B, "train_steps": args.train_steps, "keys_in_table": occ,
+        "table_slots": tr.shard.capacity, "eval": sc.result(),
+        "not_measured": ["per-phase cycles", "k = 4 and k = 8 shapes",
+                         "F = 64 (one wave per block)", "the grid cap and waves per block"],
+        **res}), flush=True)
+
+
 def csr_mode(args):
     """1 GPU: the same Criteo-shaped minibatches through the fixed-width step and through the
     ``row_ptr`` step (fm_csr), alternated window by window in this one process, then an
@@ -278,7 +370,9 @@ def main():
                          "alternated, and an rcv1-shaped valued minibatch")
     ap.add_argument("--score", action="store_true",
                     help="1 GPU: the fused scoring kernel (FMScorer) vs FMTrainer.predict on "
-                         "held-out minibatches, alternated; D in {16, 32, 64, 128} and rcv1")
+                         "held-out minibatches, alternated; D in {16, 32, 64, 128} and rcv1. With "
+                         "--ffm: the fused FFM scorer (FFMScorer) vs FFMTrainer.predict on fixed "
+                         "rows, CSR rows with slots missing and CSR rows wider than 64")
     ap.add_argument("--train-steps", type=int, default=20,
                     help="--score: training steps that fill the table first")
     ap.add_argument("--repeats", type=int, default=5, help="--csr / --score: windows per route")
@@ -295,6 +389,8 @@ def main():
     ap.add_argument("--prefetch", type=int, default=1,
                     help="generate + localise minibatch t+1 on a side stream during step t")
     args = ap.parse_args()
+    if args.ffm and args.score:
+        return ffm_score_mode(args)
     if args.ffm:
         return ffm_mode(args)
     if args.csr:

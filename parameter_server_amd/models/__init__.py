@@ -1,9 +1,10 @@
 """Model families trained through the parameter server."""
 from .ffm import FFMConfig, FFMTrainer
 from .fm import FMConfig, FMTrainer
-from .scorer import FMScorer, ModelScorer
+from .scorer import FFMScorer, FMScorer, ModelScorer
 from .sparse_lr import SparseLRConfig, SparseLRTrainer
 from .wide_deep import WideDeepConfig, WideDeepTrainer
 
 __all__ = ["SparseLRConfig", "SparseLRTrainer", "WideDeepConfig", "WideDeepTrainer", "FMConfig",
-           "FMTrainer", "FFMConfig", "FFMTrainer", "ModelScorer", "FMScorer"]
+           "FMTrainer", "FFMConfig", "FFMTrainer", "ModelScorer", "FMScorer",
+           "FFMScorer"]

@@ -26,7 +26,11 @@ order. ``fields`` [nnz] int32 then replaces the position -> field map; a field o
 keeps the occurrence's linear term and takes it out of every pair. The step is the same
 sequence with ``ffm_csr`` (ffm_csr.hip) as its forward / backward: rows of up to ``cfg.slots``
 positions run on the per-wave LDS tile with field lists built in the wave, wider rows on a
-second launch that reads partners from global memory. A fused table-probe scorer is not here.
+second launch that reads partners from global memory.
+
+Scoring a stored model is ``FFMScorer`` (models/scorer.py, ``scorer()`` below): margins, loss /
+accuracy sums and the AUC histogram of raw keys in one launch of the fused probe + field-sum
+kernel (ffm_predict.hip), rows of any width, from a live shard or a snapshot.
 """
 from __future__ import annotations
 
@@ -42,6 +46,7 @@ from ..ops.kv_table import UpdateRule, next_pow2
 from ..ops.linear import AUC_BINS, auc_from_hist, linear_backward, new_accum
 from ..ops.localize import Localizer
 from ..ops.native import hipops
+from ..ops.score import ffm_pairs, ffm_pairs_csr
 from ..parallel.comm import Comm, LocalComm
 from ..parallel.partition import KeyPartition
 from .fm import FMTrainer
@@ -196,17 +201,8 @@ class FFMTrainer(EmbeddingPS):
 
     def _pairs_torch(self, X0, x, dtype):
         """G [B, S, F, k] and the pair part of the margin [B] of expanded rows X0
-        [B*S, Dr] with values x [B, S]: gather [B, S, S, k], mask the diagonal,
-        scatter-add by the partner's field."""
-        S, F, k = self.cfg.slots, self.F, self.cfg.k
-        B = x.shape[0]
-        fl = self._fields_t.to(X0.device)
-        V = X0[:B * S, :F * k].to(dtype).reshape(B, S, F, k)
-        P = V[:, :, fl, :].transpose(1, 2)  # P[b, i, j] = v_{j, f_i}
-        off = 1.0 - torch.eye(S, dtype=dtype, device=X0.device)
-        P = P * (x[:, None, :] * off)[..., None]
-        G = torch.zeros(B, S, F, k, dtype=dtype, device=X0.device).index_add_(2, fl, P)
-        return G, 0.5 * (x * (V * G).sum((2, 3))).sum(1)
+        [B*S, Dr] with values x [B, S] (ops/score.py ``ffm_pairs``)."""
+        return ffm_pairs(X0, x, self._fields_t.to(X0.device), self.F, self.cfg.k, dtype)
 
     def _fwd_bwd_math(self, X0, vals, B, S, local_col, w_wide, labels, dtype=torch.float32):
         """(margin [B], coef [B], dX0 [B*S, Dr]) in ``dtype``, nothing rounded to bf16."""
@@ -313,34 +309,9 @@ class FFMTrainer(EmbeddingPS):
         self.examples += B
 
     def _pairs_torch_csr(self, X0, x, row_of, fld, B, dtype):
-        """``_pairs_torch`` on CSR rows: the rows are gathered into a padded [B, W] block (W
-        the widest row) where an absent position, or an occurrence whose field is outside
-        [0, F), has x = 0 and so enters no pair. Returns G [nnz, F, k] (zero for such an
-        occurrence), the pair part of the margin [B] and the masked x [nnz]."""
-        F, k = self.F, self.cfg.k
-        nnz, dev = row_of.numel(), X0.device
-        r = row_of.long()
-        width = torch.bincount(r, minlength=B)
-        W = max(int(width.max()) if nnz else 0, 1)
-        col = torch.arange(nnz, device=dev) - (torch.cumsum(width, 0) - width)[r]
-        f = fld[:nnz].long()
-        ok = (f >= 0) & (f < F)
-        x = x * ok
-        Vp = torch.zeros(B, W, F, k, dtype=dtype, device=dev)
-        Vp[r, col] = X0[:nnz, :F * k].to(dtype).reshape(nnz, F, k)
-        xp = torch.zeros(B, W, dtype=dtype, device=dev)
-        xp[r, col] = x
-        fp = torch.zeros(B, W, dtype=torch.long, device=dev)
-        fp[r, col] = torch.where(ok, f, 0)
-        bi = torch.arange(B, device=dev)[:, None, None]
-        ji = torch.arange(W, device=dev)[None, None, :]
-        P = Vp[bi, ji, fp[:, :, None]]  # P[b, i, j] = v_{j, f_i}
-        off = 1.0 - torch.eye(W, dtype=dtype, device=dev)
-        P = P * (xp[:, None, :] * off)[..., None]
-        G = torch.zeros(B, W, F, k, dtype=dtype, device=dev).scatter_add_(
-            2, fp[:, None, :, None].expand(B, W, W, k), P)
-        pair = 0.5 * (xp * (Vp * G).sum((2, 3))).sum(1)
-        return G[r, col] * ok[:, None, None], pair, x
+        """``_pairs_torch`` on CSR rows (ops/score.py ``ffm_pairs_csr``): G [nnz, F, k], the
+        pair part of the margin [B] and x [nnz] with the fields outside [0, F) masked."""
+        return ffm_pairs_csr(X0, x, row_of, fld, B, self.F, self.cfg.k, dtype)
 
     def _fwd_bwd_math_csr(self, X0, vals, row_of, fld, local_col, w_wide, labels,
                           dtype=torch.float32):
@@ -405,5 +376,19 @@ class FFMTrainer(EmbeddingPS):
             return torch.zeros(B).index_add_(0, r, w * x) + pair
         x = x.reshape(B, S)
         return (w.reshape(B, S) * x).sum(1) + self._pairs_torch(X0, x, torch.float32)[1]
+
+    def scorer(self):
+        """An ``FFMScorer`` on this trainer's own shard (no copy), with ``cfg.fields`` as its
+        position -> field map: held-out loss, accuracy and AUC through the fused scoring
+        kernel, rows of any width. G == 1. Nothing is synchronised here: score on the stream
+        the steps run on, after them."""
+        if self.G != 1:
+            raise NotImplementedError(
+                "scorer() reads the local shard (G == 1); score a sharded model with "
+                "FFMScorer.from_state_dict(FFMTrainer.merge_state_dicts(<every rank's "
+                "state_dict()>), device, num_fields, k)")
+        from .scorer import FFMScorer
+
+        return FFMScorer.from_shard(self.shard, self.bits, self.F, self.cfg.k, fields=self.fields)
 
     progress = FMTrainer.progress

@@ -15,7 +15,7 @@ import torch
 from ..ops.embedding import EmbeddingShard
 from ..ops.keymix import mix
 from ..ops.kv_table import KVTable, next_pow2
-from ..ops.score import ScoreAccum, auc_from_counts, fm_score, score
+from ..ops.score import ScoreAccum, auc_from_counts, ffm_score, fm_score, score
 
 
 class ModelScorer:
@@ -180,3 +180,82 @@ class FMScorer(ModelScorer):
 
     def _score(self, keys, **kw):
         return fm_score(self.shard, keys, self.bits, **kw)
+
+
+class FFMScorer(ModelScorer):
+    """``ModelScorer`` for a field-aware factorization machine (models/ffm.py): the model is an
+    ``EmbeddingShard`` whose rows hold ``num_fields`` vectors of ``k`` bf16, and every
+    minibatch is one launch of the fused probe + field-sum kernel (ops/score.py ``ffm_score``,
+    csrc/hip/ffm_predict.hip), for rows of any width and every geometry ``FFMConfig`` accepts.
+    ``fields``: the position -> field map of fixed-width rows (None: identity), uploaded once.
+    CSR rows bring ``fields=`` [nnz] int32, the field of every occurrence, with each call.
+    ``evaluate``, ``totals`` and ``result`` are ``ModelScorer``'s."""
+
+    def __init__(self, shard: EmbeddingShard, bits: int, num_fields: int, k: int, fields=None,
+                 loss="logit"):
+        super().__init__(shard.table, bits, loss)
+        self.shard, self.F, self.k = shard, int(num_fields), int(k)
+        if self.k not in (2, 4, 8) or self.F < 1 or self.F * self.k > shard.dim:
+            raise ValueError(f"{self.F} fields of k = {self.k} (2, 4 or 8) do not fit rows of "
+                             f"{shard.dim} columns")
+        self.fields = None if fields is None else [int(f) for f in fields]
+        if self.fields and not 0 <= min(self.fields) <= max(self.fields) < self.F:
+            raise ValueError(f"every field must lie in [0, {self.F})")
+        self._field_of = None if self.fields is None else \
+            torch.tensor(self.fields, dtype=torch.int32, device=self.device)
+
+    @classmethod
+    def from_shard(cls, shard: EmbeddingShard, bits: int, num_fields: int, k: int, fields=None,
+                   loss="logit") -> "FFMScorer":
+        """Alias an existing shard (no copy). The caller orders its own updates before the
+        scoring launches (``FFMTrainer.scorer``: the same stream)."""
+        return cls(shard, bits, num_fields, k, fields, loss)
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, device, num_fields: int, k: int,
+                        capacity: int | None = None) -> "FFMScorer":
+        """A snapshot of ``FFMTrainer.state_dict`` (or ``merge_state_dicts`` of the ranks'
+        snapshots) in a shard of its own at load <= 0.5; key width and row width come from
+        the snapshot, which does not record the fields: ``num_fields`` and ``k`` are the
+        trainer's, and must fit the rows."""
+        if str(sd.get("model")) != "FFMTrainer":
+            raise ValueError(f"snapshot of a {sd.get('model')}, not an FFMTrainer")
+        bits, dim = int(sd["bits"]), int(sd["dim"])
+        if dim < int(num_fields) * int(k):
+            raise ValueError(f"snapshot rows of {dim} columns hold no {num_fields} fields of "
+                             f"k = {k}")
+        n = sd["keys"].numel()
+        shard = EmbeddingShard(capacity or next_pow2(max(64, 2 * n)), dim, device)
+        if n:  # (check_ok inside: a capacity too small raises 'KVTable full')
+            mk = mix(sd["keys"].cpu().contiguous(), bits)
+            shard.load_state(mk, sd["w"], sd["z"], sd["n"], sd["rows"], sd["acc"],
+                             cnt=sd.get("cnt"))
+        return cls(shard, bits, num_fields, k)
+
+    def _score(self, keys, fields=None, **kw):
+        if kw.get("row_ptr") is None:
+            if fields is not None:
+                raise ValueError("fixed-width rows use the scorer's position -> field map; "
+                                 "fields= is the field of every occurrence of CSR rows")
+            fields = self._field_of
+        return ffm_score(self.shard, keys, self.bits, num_fields=self.F, k=self.k, fields=fields,
+                         **kw)
+
+    def predict(self, keys: torch.Tensor, *, row_ptr=None, width=None, vals=None,
+                fields=None) -> torch.Tensor:
+        """Margins only (nothing accumulated)."""
+        return self._score(keys, fields, row_ptr=row_ptr, width=width, vals=vals)
+
+    def score(self, keys, labels, *, row_ptr=None, width=None, vals=None, fields=None,
+              margins=True):
+        """Margins of one labelled minibatch; its sums and bins go into the accumulator."""
+        B = row_ptr.numel() - 1 if row_ptr is not None else keys.numel() // int(width)
+        return self._score(keys, fields, row_ptr=row_ptr, width=width, vals=vals, labels=labels,
+                           margins=margins, acc=self.acc, loss=self.loss, B=B)
+
+    def score_batch(self, b, margins: bool = False):
+        """One fixed-width ``DeviceBatch`` of a ``DeviceFeeder``, through the position map."""
+        if b.row_ptr is not None:
+            raise ValueError("FFMScorer.score_batch: a CSR DeviceBatch carries no field ids; "
+                             "score CSR rows with score(keys, labels, row_ptr=, fields=)")
+        return super().score_batch(b, margins)

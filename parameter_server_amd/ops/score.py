@@ -169,6 +169,126 @@ def fm_score(shard, keys: torch.Tensor, bits: int, *, row_ptr=None, width=None, 
     return m if margins else None
 
 
+def ffm_pairs(X0, x, fl, F: int, k: int, dtype):
+    """The field-aware pairs of fixed-width rows in PyTorch: expanded rows X0 [B*S, Dr],
+    values x [B, S], ``fl`` [S] (long) position -> field in [0, F). Gather [B, S, S, k], mask
+    the diagonal, scatter-add by the partner's field. Returns G [B, S, F, k] with G[b, i, f] =
+    sum_{j != i, f_j = f} x_j v_{j, f_i} and the pair part of the margin [B]."""
+    B, S = x.shape
+    V = X0[:B * S, :F * k].to(dtype).reshape(B, S, F, k)
+    P = V[:, :, fl, :].transpose(1, 2)  # P[b, i, j] = v_{j, f_i}
+    off = 1.0 - torch.eye(S, dtype=dtype, device=X0.device)
+    P = P * (x[:, None, :] * off)[..., None]
+    G = torch.zeros(B, S, F, k, dtype=dtype, device=X0.device).index_add_(2, fl, P)
+    return G, 0.5 * (x * (V * G).sum((2, 3))).sum(1)
+
+
+def ffm_pairs_csr(X0, x, row_of, fld, B: int, F: int, k: int, dtype):
+    """``ffm_pairs`` on CSR rows with a field per occurrence: the rows are gathered into a
+    padded [B, W] block (W the widest row) where an absent position, or an occurrence whose
+    field is outside [0, F), has x = 0 and so enters no pair. Returns G [nnz, F, k] (zero for
+    such an occurrence), the pair part of the margin [B] and the masked x [nnz]."""
+    nnz, dev = row_of.numel(), X0.device
+    r = row_of.long()
+    width = torch.bincount(r, minlength=B)
+    W = max(int(width.max()) if nnz else 0, 1)
+    col = torch.arange(nnz, device=dev) - (torch.cumsum(width, 0) - width)[r]
+    f = fld[:nnz].long()
+    ok = (f >= 0) & (f < F)
+    x = x * ok
+    Vp = torch.zeros(B, W, F, k, dtype=dtype, device=dev)
+    Vp[r, col] = X0[:nnz, :F * k].to(dtype).reshape(nnz, F, k)
+    xp = torch.zeros(B, W, dtype=dtype, device=dev)
+    xp[r, col] = x
+    fp = torch.zeros(B, W, dtype=torch.long, device=dev)
+    fp[r, col] = torch.where(ok, f, 0)
+    bi = torch.arange(B, device=dev)[:, None, None]
+    ji = torch.arange(W, device=dev)[None, None, :]
+    P = Vp[bi, ji, fp[:, :, None]]  # P[b, i, j] = v_{j, f_i}
+    off = 1.0 - torch.eye(W, dtype=dtype, device=dev)
+    P = P * (xp[:, None, :] * off)[..., None]
+    G = torch.zeros(B, W, F, k, dtype=dtype, device=dev).scatter_add_(
+        2, fp[:, None, :, None].expand(B, W, W, k), P)
+    pair = 0.5 * (xp * (Vp * G).sum((2, 3))).sum(1)
+    return G[r, col] * ok[:, None, None], pair, x
+
+
+def ffm_score(shard, keys: torch.Tensor, bits: int, *, num_fields: int, k: int, row_ptr=None,
+              width=None, fields=None, vals=None, labels=None, margins: bool = True,
+              acc: ScoreAccum | None = None, loss="logit", B: int | None = None):
+    """``score`` for a field-aware factorization machine: ``shard`` is an ``EmbeddingShard``
+    whose rows hold ``num_fields`` vectors of ``k`` bf16 (models/ffm.py); margin = x.w +
+    sum_{i<j} x_i x_j <v_{i,f_j}, v_{j,f_i}>, a key the model does not hold contributing
+    nothing. With ``row_ptr``, ``fields`` is int32 [nnz], the field of every occurrence (one
+    outside [0, F) keeps its linear term and enters no pair); with a fixed ``width`` it is the
+    position -> field map (int32 [width] on the keys' device, or a list; None: identity).
+    GPU: one ``ffm_predict_rows`` launch (csrc/hip/ffm_predict.hip), rows of any width; CPU:
+    the PyTorch ops of ``FFMTrainer.predict``, in f32."""
+    if (row_ptr is None) == (not width):
+        raise ValueError("ffm_score needs row_ptr or a fixed width, not both")
+    if acc is not None and labels is None:
+        raise ValueError("ffm_score: an accumulator needs labels")
+    F, k = int(num_fields), int(k)
+    if k not in (2, 4, 8) or F < 1 or F * k > shard.dim:
+        raise ValueError(f"ffm_score: {F} fields of k = {k} (2, 4 or 8) do not fit rows of "
+                         f"{shard.dim} columns")
+    keys = keys.contiguous()
+    nnz = keys.numel()
+    dev = keys.device
+    if row_ptr is not None:
+        if fields is None or not isinstance(fields, torch.Tensor) or \
+                fields.dtype != torch.int32 or fields.numel() != nnz:
+            raise ValueError(f"ffm_score: rows by row_ptr need fields, int32 [{nnz}]")
+    elif fields is None:
+        if int(width) > F:
+            raise ValueError(f"ffm_score: rows of {int(width)} positions on {F} fields need a "
+                             "position -> field map")
+    else:
+        if not isinstance(fields, torch.Tensor):
+            fields = torch.tensor([int(f) for f in fields], dtype=torch.int32, device=dev)
+        if fields.dtype != torch.int32 or fields.numel() != int(width):
+            raise ValueError(f"ffm_score: the position -> field map must be int32 [{int(width)}]")
+    if fields is not None and fields.device.type != dev.type:
+        raise ValueError(f"ffm_score: fields must be on the keys' device ({dev})")
+    if B is None:
+        B = row_ptr.numel() - 1 if row_ptr is not None else nnz // int(width)
+    L = loss_id(loss)
+    table = shard.table
+    if is_gpu(keys):
+        m = torch.empty(B, dtype=torch.float32, device=dev) if margins else None
+        if B:
+            csr = row_ptr is not None
+            hipops().ffm_predict_rows(table.slots, table.home_base, table.home_m, shard.rows, keys,
+                                      bits, F, k, row_ptr, int(width or 0),
+                                      fields if csr else None, None if csr else fields, vals,
+                                      labels, B, L, m, acc.metrics if acc is not None else None,
+                                      acc.hist if acc is not None else None, AUC_BINS)
+        return m
+    if B == 0:
+        return torch.empty(0, dtype=torch.float32) if margins else None
+    slot, w = table.resolve(mix(keys, bits), insert=False)
+    ok = slot >= 0
+    w = torch.where(ok, w, torch.zeros_like(w))
+    X0 = torch.zeros(nnz, shard.dim, device=dev)
+    X0[ok] = shard.rows[slot[ok]].float()
+    x = vals.float() if vals is not None else torch.ones(nnz)
+    if row_ptr is not None:
+        r = torch.repeat_interleave(torch.arange(B), row_ptr[1:B + 1] - row_ptr[:B])
+        n = r.numel()
+        pair = ffm_pairs_csr(X0[:n], x[:n], r, fields, B, F, k, torch.float32)[1]
+        m = torch.zeros(B).index_add_(0, r, w[:n] * x[:n]) + pair
+    else:
+        S = int(width)
+        fl = torch.arange(S) if fields is None else fields.long()
+        if int(fl.min()) < 0 or int(fl.max()) >= F:
+            raise ValueError(f"ffm_score: every field of the position map must lie in [0, {F})")
+        x = x[:B * S].reshape(B, S)
+        m = (w[:B * S].reshape(B, S) * x).sum(1) + ffm_pairs(X0, x, fl, F, k, torch.float32)[1]
+    if acc is not None:
+        _accumulate(acc, m, labels, B, L)
+    return m if margins else None
+
+
 def row_bound(keys: torch.Tensor, w_of: dict, vals=None, row_ptr=None, width=None):
     """fp64 reference margins by a dictionary loop over the raw keys (no mixing, no table)
     and the derived f32 bound per row, (n_r + 2) 2^-23 sum |w x|: n_r products rounded once
