@@ -360,8 +360,63 @@ def ffm_mode(args):
         "train": {n: tr.progress() for n, tr in trainers.items()}, "all_ms": ms}), flush=True)
 
 
+def fwfm_mode(args):
+    """1 GPU: the field-weighted FM step (models/fwfm.py, fwfm.hip; D = 16, one field per slot,
+    F = 39) on Criteo-shaped minibatches against the FM step at D = 16 and the FFM step at
+    k = 2 (rows of 80), all three in this one process, alternated window by window. Step
+    times by a host clock around synchronised windows."""
+    from parameter_server_amd.models.ffm import FFMConfig, FFMTrainer
+    from parameter_server_amd.models.fm import FMConfig, FMTrainer
+    from parameter_server_amd.models.fwfm import FwFMConfig, FwFMTrainer
+    from parameter_server_amd.ops.synthetic import criteo_batch
+
+    dev = torch.device("cuda", 0)
+    B, N = args.minibatch, int(args.num_features)
+    slots = min(args.table_slots, 1 << 24)  # three tables side by side
+    crit = [criteo_batch(B, seed=77, row0=i * B, num_features=N, device=dev) for i in range(8)]
+    common = dict(localize=args.localize, num_features=N, minibatch=B, table_capacity=slots, seed=0)
+    trainers = {"fm_D16": FMTrainer(FMConfig(embedding_dim=16, **common), device=dev),
+                "fwfm_D16_F39": FwFMTrainer(FwFMConfig(embedding_dim=16, **common), device=dev),
+                "ffm_k2_F39": FFMTrainer(FFMConfig(k=2, **common), device=dev)}
+    routes = {name: (lambda i, tr=tr: tr.step(*crit[i % len(crit)]))
+              for name, tr in trainers.items()}
+
+    def window(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            fn(i)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps * 1e3
+
+    for fn in routes.values():
+        for i in range(args.warmup):
+            fn(i)
+    ms = {name: [] for name in routes}
+    for r in range(args.repeats):
+        for name, fn in routes.items():
+            ms[name].append(window(fn))
+        print(f"window {r}: " + "  ".join(f"{n} {v[-1]:.3f} ms" for n, v in ms.items()),
+              flush=True)
+    med = {n: sorted(v)[len(v) // 2] for n, v in ms.items()}
+    R = trainers["fwfm_D16_F39"].R
+    print(json.dumps({
+        "metric": "FwFM step time (fwfm.hip) vs the FM step at D = 16 and the FFM step at k = 2, "
+                  "1 GPU",
+        "unit": "ms/step (median of windows)", "steps_per_window": args.steps,
+        "windows": args.repeats, "minibatch": B, "slots": 39, "median_ms": med,
+        "min_ms": {n: min(v) for n, v in ms.items()}, "max_ms": {n: max(v) for n, v in ms.items()},
+        "fwfm_over_fm": med["fwfm_D16_F39"] / med["fm_D16"],
+        "fwfm_over_ffm": med["fwfm_D16_F39"] / med["ffm_k2_F39"],
+        "R_min_max": [float(R.min()), float(R.max())],
+        "train": {n: tr.progress() for n, tr in trainers.items()}, "all_ms": ms}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fwfm", action="store_true",
+                    help="1 GPU: the field-weighted FM step (D = 16, F = 39) vs the FM step at "
+                         "D = 16 and the FFM step at k = 2, alternated")
     ap.add_argument("--ffm", action="store_true",
                     help="1 GPU: the field-aware FM step (k = 2, and k = 4 on 27 fields) vs the same "
                          "step with the PyTorch forward / backward and the FM step, alternated")
@@ -389,6 +444,8 @@ def main():
     ap.add_argument("--prefetch", type=int, default=1,
                     help="generate + localise minibatch t+1 on a side stream during step t")
     args = ap.parse_args()
+    if args.fwfm:
+        return fwfm_mode(args)
     if args.ffm and args.score:
         return ffm_score_mode(args)
     if args.ffm:

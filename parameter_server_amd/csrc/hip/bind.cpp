@@ -666,4 +666,5 @@ PYBIND11_MODULE(_hipops, m) {
   register_scoretext(m);
   register_slotsplit(m);
   register_ffm(m);
+  register_fwfm(m);
 }

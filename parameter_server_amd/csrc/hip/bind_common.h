@@ -35,6 +35,7 @@ void register_dense(py::module_& m);     // Darlin BCD, GEMMs, embedding, spmv
 void register_scoretext(py::module_& m); // prediction lines
 void register_slotsplit(py::module_& m); // split by feature group
 void register_ffm(py::module_& m);       // field-aware FM
+void register_fwfm(py::module_& m);      // field-weighted FM
 
 inline hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 

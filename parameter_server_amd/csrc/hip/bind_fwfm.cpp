@@ -1,0 +1,134 @@
+// Bindings of the field-weighted factorization machine (fwfm.hip).
+#include "bind_common.h"
+#include "fwfm.h"
+
+using namespace psamd_bind;
+
+namespace {
+
+int padded_fields(int F) { return (F + 15) / 16 * 16; }
+
+// what the two row ops share: the geometry, the factor rows, the occurrences, R. `fields`
+// must outlive the launch call (the launcher reads it on the host).
+psamd::Fwfm check_fwfm(const Tensor& rows, const optional<Tensor>& idx,
+                       const optional<Tensor>& vals, int64_t B, int S,
+                       const std::vector<int32_t>& fields, int F, const Tensor& R,
+                       const optional<Tensor>& local_col, const Tensor& w_local) {
+  psamd::Fwfm a = {};
+  chk(rows, at::kBFloat16, "rows");
+  chk(w_local, at::kFloat, "w_local");
+  chk(R, at::kFloat, "R");
+  check(rows.dim() == 2, "rows [R, D]");
+  check(S >= 1 && S <= 64, "fwfm: 1..64 positions per row");
+  check(F >= 1 && F <= 64, "fwfm: 1..64 fields");
+  check(rows.size(1) == 8 || rows.size(1) == 16 || rows.size(1) == 32,
+        "fwfm: rows of D in {8, 16, 32} columns");
+  check(R.numel() == (int64_t)F * F, "fwfm: R [F, F]");
+  check((int64_t)fields.size() == S, "fwfm: one field per position");
+  for (int32_t f : fields) check(f >= 0 && f < F, "fwfm: field outside [0, F)");
+  check(B >= 0 && B * S < (int64_t(1) << 31), "fwfm: 0 <= B * S < 2^31");
+  a.B = B;
+  a.S = S;
+  a.F = F;
+  a.Dr = (int)rows.size(1);
+  a.fields = fields.data();
+  a.local_col = optr<int32_t>(local_col, at::kInt, "local_col");
+  if (a.local_col) check(local_col->numel() >= B * S, "local_col too small");
+  a.vals = optr<float>(vals, at::kFloat, "vals");
+  if (a.vals) check(vals->numel() >= B * S, "vals too small");
+  a.rows = rows.data_ptr();
+  a.rows_cap = rows.size(0);
+  a.idx = optr<int64_t>(idx, at::kLong, "idx");
+  a.idx_cap = a.idx ? idx->numel() : 0;
+  a.w_local = ptr<float>(w_local);
+  a.w_cap = w_local.numel();
+  a.R = ptr<float>(R);
+  return a;
+}
+
+// dR_part [parts, Fp * Fp] f32: the number of partials is the tensor's first dimension
+int check_parts(const Tensor& dR_part, int F) {
+  chk(dR_part, at::kFloat, "dR_part");
+  const int64_t fp2 = (int64_t)padded_fields(F) * padded_fields(F);
+  check(dR_part.dim() == 2 && dR_part.size(1) == fp2 && dR_part.size(0) >= 1 &&
+            dR_part.size(0) <= 4096,
+        "fwfm: dR_part [1..4096, Fp * Fp], Fp = F rounded up to 16");
+  return (int)dR_part.size(0);
+}
+
+}  // namespace
+
+void psamd_bind::register_fwfm(py::module_& m) {
+  // rows [R, D] bf16 read through local_col (None: column = position) and idx (None: the
+  // column is the row); fields [S] ints in [0, F), one map for all rows; R [F, F] f32, read
+  // as symmetric from its upper triangle. One block per row of dR_part, each writes its
+  // partial of dR (fwfm_dr_reduce sums them).
+  m.def("fwfm_fwd_bwd", [](Tensor rows, optional<Tensor> idx, optional<Tensor> vals, int64_t B,
+                           int S, std::vector<int32_t> fields, int F, Tensor R,
+                           optional<Tensor> local_col, Tensor w_local, Tensor labels, Tensor coef,
+                           Tensor dX0, Tensor dR_part, Tensor metrics, optional<Tensor> hist,
+                           int nbins) {
+    psamd::Fwfm a = check_fwfm(rows, idx, vals, B, S, fields, F, R, local_col, w_local);
+    chk(labels, at::kFloat, "labels");
+    chk(coef, at::kFloat, "coef");
+    chk(dX0, at::kBFloat16, "dX0");
+    chk(metrics, at::kDouble, "metrics");
+    check(labels.numel() >= B && coef.numel() >= B, "labels/coef too small");
+    check(dX0.numel() >= B * S * a.Dr, "dX0 too small");
+    check(metrics.numel() >= 3, "metrics[3]");
+    a.parts = check_parts(dR_part, F);
+    a.dR_part = ptr<float>(dR_part);
+    a.hist = optr<uint32_t>(hist, at::kInt, "hist");
+    if (a.hist) check(nbins > 0 && hist->numel() >= 2 * nbins, "hist too small");
+    a.labels = ptr<float>(labels);
+    a.coef = ptr<float>(coef);
+    a.dX0 = dX0.data_ptr();
+    a.metrics = ptr<double>(metrics);
+    a.nbins = nbins;
+    a.acc_stripes = acc_stripes_of(metrics);
+    psamd::fwfm_fwd_bwd(a, cur_stream());
+  });
+  // the forward-only form: margins [B] and nothing else
+  m.def("fwfm_margins", [](Tensor rows, optional<Tensor> idx, optional<Tensor> vals, int64_t B,
+                           int S, std::vector<int32_t> fields, int F, Tensor R,
+                           optional<Tensor> local_col, Tensor w_local, Tensor margins) {
+    psamd::Fwfm a = check_fwfm(rows, idx, vals, B, S, fields, F, R, local_col, w_local);
+    chk(margins, at::kFloat, "margins");
+    check(margins.numel() >= B, "margins too small");
+    a.margins = ptr<float>(margins);
+    psamd::fwfm_margins(a, cur_stream());
+  });
+  // sum: dR [F, F] = the partials in a fixed order, mirrored. update: AdaGrad on R and acc
+  // [F, F] with g = dR + lambda_r R. Both in one launch on one rank; sum, an all-reduce of
+  // dR, then update on several.
+  m.def("fwfm_dr_reduce", [](optional<Tensor> dR_part, Tensor dR, int F, bool sum, bool update,
+                             optional<Tensor> R, optional<Tensor> acc, double lr,
+                             double lambda_r) {
+    psamd::FwfmReduce a = {};
+    check(F >= 1 && F <= 64, "fwfm_dr_reduce: 1..64 fields");
+    check(sum || update, "fwfm_dr_reduce: sum, update or both");
+    chk(dR, at::kFloat, "dR");
+    check(dR.numel() == (int64_t)F * F, "fwfm_dr_reduce: dR [F, F]");
+    a.F = F;
+    a.dR = ptr<float>(dR);
+    a.sum = sum;
+    a.update = update;
+    if (sum) {
+      check(dR_part.has_value() && dR_part->defined(), "fwfm_dr_reduce: sum needs dR_part");
+      a.parts = check_parts(*dR_part, F);
+      a.dR_part = ptr<float>(*dR_part);
+    }
+    if (update) {
+      a.R = optr<float>(R, at::kFloat, "R");
+      a.acc = optr<float>(acc, at::kFloat, "acc");
+      check(a.R && a.acc && R->numel() == (int64_t)F * F && acc->numel() == (int64_t)F * F,
+            "fwfm_dr_reduce: the update needs R and acc [F, F]");
+      check(lr > 0, "fwfm_dr_reduce: lr > 0");
+      a.lr = (float)lr;
+      a.lambda_r = (float)lambda_r;
+    }
+    psamd::fwfm_dr_reduce(a, cur_stream());
+  }, py::arg("dR_part"), py::arg("dR"), py::arg("F"), py::arg("sum"), py::arg("update"),
+     py::arg("R") = py::none(), py::arg("acc") = py::none(), py::arg("lr") = 0.0,
+     py::arg("lambda_r") = 0.0);
+}
