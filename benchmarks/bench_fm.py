@@ -363,8 +363,9 @@ def ffm_mode(args):
 def fwfm_mode(args):
     """1 GPU: the field-weighted FM step (models/fwfm.py, fwfm.hip; D = 16, one field per slot,
     F = 39) on Criteo-shaped minibatches against the FM step at D = 16 and the FFM step at
-    k = 2 (rows of 80), all three in this one process, alternated window by window. Step
-    times by a host clock around synchronised windows."""
+    k = 2 (rows of 80), and the FwFM's CSR step (fwfm_csr.hip) on the same rows, on rows with
+    slots missing and on rows widened past 64 positions, all in this one process, alternated
+    window by window. Step times by a host clock around synchronised windows."""
     from parameter_server_amd.models.ffm import FFMConfig, FFMTrainer
     from parameter_server_amd.models.fm import FMConfig, FMTrainer
     from parameter_server_amd.models.fwfm import FwFMConfig, FwFMTrainer
@@ -380,6 +381,39 @@ def fwfm_mode(args):
                 "ffm_k2_F39": FFMTrainer(FFMConfig(k=2, **common), device=dev)}
     routes = {name: (lambda i, tr=tr: tr.step(*crit[i % len(crit)]))
               for name, tr in trainers.items()}
+    # the CSR step (fwfm_csr.hip, a field id per occurrence): (a) the same full rows (row_ptr =
+    # 39 b, fields = the slot index) against the fixed-width step above, (b) each slot present
+    # with probability 0.75, (c) a quarter of the rows widened to 65..130 positions with the
+    # keys of the rows after them (fields repeat there: the diagonal of R acts)
+    slot_of = torch.arange(39, dtype=torch.int32, device=dev).repeat(B)
+    uniform = torch.arange(B + 1, device=dev) * 39
+    g = torch.Generator(device=dev).manual_seed(5)
+    full, missing, wide = [], [], []
+    for k39, lab in crit:
+        full.append((k39, lab, uniform, slot_of))
+        keep = torch.rand(B * 39, device=dev, generator=g) < 0.75
+        rp = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        rp[1:] = torch.cumsum(keep.view(B, 39).sum(1), 0)
+        missing.append((k39[keep], lab, rp, slot_of[keep]))
+        width = torch.where(torch.rand(B, device=dev, generator=g) < 0.25,
+                            torch.randint(65, 131, (B,), device=dev, generator=g), 39)
+        rp = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        rp[1:] = torch.cumsum(width, 0)
+        row = torch.repeat_interleave(torch.arange(B, device=dev), width)
+        pos = torch.arange(int(rp[-1]), device=dev) - rp[row]
+        wide.append((k39.view(B, 39)[(row + pos // 39) % B, pos % 39].contiguous(), lab, rp,
+                     (pos % 39).int()))
+    wide_cfg = dict(common, slots=64, fields=[i % 39 for i in range(64)])  # max_nnz = 64 B
+    for tag, data, kw in (("full", full, common), ("missing", missing, common),
+                          ("wide", wide, wide_cfg)):
+        tr = trainers[f"fwfm_csr_{tag}"] = FwFMTrainer(FwFMConfig(embedding_dim=16, **kw),
+                                                       device=dev)
+
+        def csr(i, tr=tr, data=data):
+            k, lab, rp, fl = data[i % len(data)]
+            tr.step(k, lab, row_ptr=rp, fields=fl)
+
+        routes[f"fwfm_csr_{tag}"] = csr
 
     def window(fn):
         torch.cuda.synchronize()
@@ -408,6 +442,9 @@ def fwfm_mode(args):
         "min_ms": {n: min(v) for n, v in ms.items()}, "max_ms": {n: max(v) for n, v in ms.items()},
         "fwfm_over_fm": med["fwfm_D16_F39"] / med["fm_D16"],
         "fwfm_over_ffm": med["fwfm_D16_F39"] / med["ffm_k2_F39"],
+        "csr_over_fixed": med["fwfm_csr_full"] / med["fwfm_D16_F39"],
+        "csr_nnz": {"full": B * 39, "missing": [int(x[0].numel()) for x in missing[:2]],
+                    "wide": [int(x[0].numel()) for x in wide[:2]]},
         "R_min_max": [float(R.min()), float(R.max())],
         "train": {n: tr.progress() for n, tr in trainers.items()}, "all_ms": ms}), flush=True)
 

@@ -1,4 +1,4 @@
-// Bindings of the field-weighted factorization machine (fwfm.hip).
+// Bindings of the field-weighted factorization machine (fwfm.hip, fwfm_csr.hip).
 #include "bind_common.h"
 #include "fwfm.h"
 
@@ -36,6 +36,46 @@ psamd::Fwfm check_fwfm(const Tensor& rows, const optional<Tensor>& idx,
   if (a.local_col) check(local_col->numel() >= B * S, "local_col too small");
   a.vals = optr<float>(vals, at::kFloat, "vals");
   if (a.vals) check(vals->numel() >= B * S, "vals too small");
+  a.rows = rows.data_ptr();
+  a.rows_cap = rows.size(0);
+  a.idx = optr<int64_t>(idx, at::kLong, "idx");
+  a.idx_cap = a.idx ? idx->numel() : 0;
+  a.w_local = ptr<float>(w_local);
+  a.w_cap = w_local.numel();
+  a.R = ptr<float>(R);
+  return a;
+}
+
+// the CSR ops: row_ptr [B + 1] int64, fld [nnz] int32 (device), everything per occurrence
+// holds at least nnz entries
+psamd::FwfmCsr check_fwfm_csr(const Tensor& row_ptr, const Tensor& fld, int64_t nnz,
+                              const Tensor& rows, const optional<Tensor>& idx,
+                              const optional<Tensor>& vals, int64_t B, int F, const Tensor& R,
+                              const optional<Tensor>& local_col, const Tensor& w_local) {
+  psamd::FwfmCsr a = {};
+  chk(row_ptr, at::kLong, "row_ptr");
+  chk(fld, at::kInt, "fields");
+  chk(rows, at::kBFloat16, "rows");
+  chk(w_local, at::kFloat, "w_local");
+  chk(R, at::kFloat, "R");
+  check(rows.dim() == 2, "rows [R, D]");
+  check(F >= 1 && F <= 64, "fwfm_csr: 1..64 fields");
+  check(rows.size(1) == 8 || rows.size(1) == 16 || rows.size(1) == 32,
+        "fwfm_csr: rows of D in {8, 16, 32} columns");
+  check(R.numel() == (int64_t)F * F, "fwfm_csr: R [F, F]");
+  check(B >= 0 && nnz >= 0 && nnz < (int64_t(1) << 31), "fwfm_csr: B >= 0, 0 <= nnz < 2^31");
+  check(row_ptr.numel() >= B + 1, "row_ptr too small");
+  check(fld.numel() >= nnz, "fields too small");
+  a.row_ptr = ptr<int64_t>(row_ptr);
+  a.fld = ptr<int32_t>(fld);
+  a.B = B;
+  a.nnz = nnz;
+  a.F = F;
+  a.Dr = (int)rows.size(1);
+  a.local_col = optr<int32_t>(local_col, at::kInt, "local_col");
+  if (a.local_col) check(local_col->numel() >= nnz, "local_col too small");
+  a.vals = optr<float>(vals, at::kFloat, "vals");
+  if (a.vals) check(vals->numel() >= nnz, "vals too small");
   a.rows = rows.data_ptr();
   a.rows_cap = rows.size(0);
   a.idx = optr<int64_t>(idx, at::kLong, "idx");
@@ -97,6 +137,48 @@ void psamd_bind::register_fwfm(py::module_& m) {
     check(margins.numel() >= B, "margins too small");
     a.margins = ptr<float>(margins);
     psamd::fwfm_margins(a, cur_stream());
+  });
+  // CSR rows of any width with a field per occurrence (fwfm_csr.hip): row_ptr [B + 1] int64,
+  // fld [nnz] int32; also writes row_of [nnz]. One block per row of dR_part, as fwfm_fwd_bwd.
+  m.def("fwfm_csr", [](Tensor row_ptr, Tensor fld, int64_t nnz, Tensor rows, optional<Tensor> idx,
+                       optional<Tensor> vals, int64_t B, int F, Tensor R,
+                       optional<Tensor> local_col, Tensor w_local, Tensor labels, Tensor coef,
+                       Tensor dX0, Tensor row_of, Tensor dR_part, Tensor metrics,
+                       optional<Tensor> hist, int nbins) {
+    psamd::FwfmCsr a = check_fwfm_csr(row_ptr, fld, nnz, rows, idx, vals, B, F, R, local_col,
+                                      w_local);
+    chk(labels, at::kFloat, "labels");
+    chk(coef, at::kFloat, "coef");
+    chk(dX0, at::kBFloat16, "dX0");
+    chk(row_of, at::kInt, "row_of");
+    chk(metrics, at::kDouble, "metrics");
+    check(labels.numel() >= B && coef.numel() >= B, "labels/coef too small");
+    check(dX0.numel() >= nnz * a.Dr, "dX0 too small");
+    check(row_of.numel() >= nnz, "row_of too small");
+    check(metrics.numel() >= 3, "metrics[3]");
+    a.parts = check_parts(dR_part, F);
+    a.dR_part = ptr<float>(dR_part);
+    a.hist = optr<uint32_t>(hist, at::kInt, "hist");
+    if (a.hist) check(nbins > 0 && hist->numel() >= 2 * nbins, "hist too small");
+    a.labels = ptr<float>(labels);
+    a.coef = ptr<float>(coef);
+    a.dX0 = dX0.data_ptr();
+    a.row_of = ptr<int32_t>(row_of);
+    a.metrics = ptr<double>(metrics);
+    a.nbins = nbins;
+    a.acc_stripes = acc_stripes_of(metrics);
+    psamd::fwfm_csr_fwd_bwd(a, cur_stream());
+  });
+  m.def("fwfm_csr_margins", [](Tensor row_ptr, Tensor fld, int64_t nnz, Tensor rows,
+                               optional<Tensor> idx, optional<Tensor> vals, int64_t B, int F,
+                               Tensor R, optional<Tensor> local_col, Tensor w_local,
+                               Tensor margins) {
+    psamd::FwfmCsr a = check_fwfm_csr(row_ptr, fld, nnz, rows, idx, vals, B, F, R, local_col,
+                                      w_local);
+    chk(margins, at::kFloat, "margins");
+    check(margins.numel() >= B, "margins too small");
+    a.margins = ptr<float>(margins);
+    psamd::fwfm_csr_margins(a, cur_stream());
   });
   // sum: dR [F, F] = the partials in a fixed order, mirrored. update: AdaGrad on R and acc
   // [F, F] with g = dR + lambda_r R. Both in one launch on one rank; sum, an all-reduce of

@@ -1,5 +1,6 @@
 // Host entry points of fwfm.hip: the field-weighted factorization machine's fused forward /
-// backward on rows of a fixed width S <= 64, and the fixed-order reduction of its dR partials.
+// backward on rows of a fixed width S <= 64, and the fixed-order reduction of its dR partials;
+// of fwfm_csr.hip: the same on CSR rows of any width with a field per occurrence.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -56,5 +57,42 @@ struct FwfmReduce {
   float lr, lambda_r;
 };
 void fwfm_dr_reduce(const FwfmReduce& a, hipStream_t st);
+
+// fwfm_csr.hip: the same model on CSR rows of any width with a field per occurrence. Row b
+// holds positions [row_ptr[b], row_ptr[b + 1]), both ends clamped to nnz; occurrence p has
+// field fld[p]. A field outside [0, F) keeps the occurrence's linear term and takes it out of
+// every pair (its dX0 row is zero). R[f][f] acts in a row where field f occurs at least
+// twice, and there only: elsewhere it adds exactly 0 to the margin, dX0 and dR[f][f]. Rows,
+// idx, local_col, w_local and R as Fwfm; dR_part as Fwfm's, for fwfm_dr_reduce.
+struct FwfmCsr {
+  const int64_t* row_ptr;  // [B + 1]
+  int64_t B, nnz;
+  int F, Dr;
+  const int32_t* fld;      // [nnz], DEVICE memory
+  const int32_t* local_col;
+  const float* vals;
+  const void* rows;  // [rows_cap, Dr] bf16
+  const int64_t* idx;
+  int64_t idx_cap, rows_cap;
+  const float* w_local;
+  int64_t w_cap;
+  const float* R;  // [F, F], DEVICE memory
+  // training form (fwfm_csr_fwd_bwd): everything below but margins; forward-only form
+  // (fwfm_csr_margins): margins alone
+  const float* labels;
+  float* coef;      // [B]
+  void* dX0;        // [nnz, Dr] bf16
+  int32_t* row_of;  // [nnz] row id of every occurrence
+  float* dR_part;   // [parts, Fp * Fp]: the launch has exactly `parts` blocks
+  int parts;
+  double* metrics;
+  uint32_t* hist;   // may be null
+  int nbins, acc_stripes;
+  float* margins;   // [B]
+};
+// F in 1..64, Dr in {8, 16, 32}, nnz < 2^31, parts in 1..4096: anything else throws
+// std::invalid_argument before a launch.
+void fwfm_csr_fwd_bwd(const FwfmCsr& a, hipStream_t st);
+void fwfm_csr_margins(const FwfmCsr& a, hipStream_t st);
 
 }  // namespace psamd

@@ -16,7 +16,24 @@ per example, both matrix products on the fp32 matrix instructions) in the middle
 fixed-order reduction of the dR partials and the AdaGrad step of R (``fwfm_dr_reduce``; G > 1:
 sum, all-reduce, update).
 
-Not here yet: CSR rows, a fused table-probe scorer and the app's ``.conf`` route.
+``step(..., row_ptr=, fields=)`` / ``predict(..., row_ptr=, fields=)`` take CSR minibatches with
+a field id per occurrence (libffm's ``field:index:value`` rows; the device text parsers' CSR
+arrays): rows of any width, fields missing, repeated, in any order. ``fields`` [nnz] int32 then
+replaces the position -> field map (``cfg.fields`` is not consulted, ``cfg.slots`` only sizes
+``max_nnz = minibatch * slots``); a field outside [0, F) keeps the occurrence's linear term and
+takes it out of every pair. A field may repeat in one row and not in the next, so the diagonal
+of R is kept out of ``T`` and acts per row, where the field occurs n_f >= 2 times:
+
+    T0       = R0 P  (R0: R with a zero diagonal),   s_f = n_f >= 2 ? 1/2 (|P[f]|^2 - q_f) : 0
+    m        = lin + 1/2 sum_f <P[f], T0[f]> + sum_f R[f][f] s_f
+    dX0[p]   = c x_p (T0[f_p] + (n_{f_p} >= 2 ? R[f_p][f_p] (P[f_p] - x_p v_p) : 0))
+    dR[f,g]  = sum_b c <P[f], P[g]> (f != g),   dR[f,f] = sum_b c s_f
+
+which on rows of one width and one map is the model above. The step is ``FFMTrainer``'s CSR
+sequence with ``fwfm_csr`` (fwfm_csr.hip: one kernel for every width, a row walked in rounds
+of 64 occurrences) in the middle and the same reduce + update of R after it.
+
+Not here yet: a fused table-probe scorer and the app's ``.conf`` route.
 """
 from __future__ import annotations
 
@@ -122,16 +139,22 @@ class FwFMTrainer(EmbeddingPS):
             Fp = (F + 15) // 16 * 16
             self.dR_part = torch.empty(min(MAX_PARTS, (B + 7) // 8), Fp * Fp,
                                        dtype=torch.float32, device=dev)
+            self.row_of = None  # [max_nnz] int32, on the first CSR step
         self.step_count = 0
         self.examples = 0
         self.t0 = time.time()
 
     # ------------------------------------------------------------------ step
     def step(self, keys: torch.Tensor, labels: torch.Tensor, vals: torch.Tensor | None = None,
-             loc=None):
+             loc=None, row_ptr: torch.Tensor | None = None, fields: torch.Tensor | None = None):
         """One minibatch: ``keys`` [B*S] raw feature ids (row-major, S per example),
-        ``labels`` [B] in {-1, +1} (or {0, 1}), optional feature values ``vals`` [B*S].
+        ``labels`` [B] in {-1, +1} (or {0, 1}), optional feature values ``vals`` [B*S]. With
+        ``row_ptr`` [B + 1] (int64) and ``fields`` [nnz] (int32, on the trainer's device) the
+        rows have any width and every occurrence names its own field (``cfg.fields`` is not
+        used): row b holds keys[row_ptr[b]:row_ptr[b + 1]].
         Nothing here reads device data on the host."""
+        if row_ptr is not None or fields is not None:
+            return self._step_csr(keys, labels, vals, loc, row_ptr, fields)
         cfg = self.cfg
         S, D = cfg.slots, cfg.embedding_dim
         B = labels.numel()
@@ -244,18 +267,132 @@ class FwFMTrainer(EmbeddingPS):
 
     _account = FFMTrainer._account
 
+    # ------------------------------------------------------------------ CSR rows
+    _check_csr = FFMTrainer._check_csr
+
+    def _step_csr(self, keys, labels, vals, loc, row_ptr, fields):
+        """step() on CSR rows with a field per occurrence: ``FFMTrainer._step_csr``'s sequence
+        with ``fwfm_csr`` (fwfm_csr.hip) as its forward / backward, which also writes the row
+        id of every occurrence for the wide gradient, then the reduce + update of R.
+        ``cfg.slots`` sizes ``max_nnz`` and is no limit on a row's width. Nothing here reads
+        device data on the host."""
+        cfg = self.cfg
+        D = cfg.embedding_dim
+        B, nnz = labels.numel(), keys.numel()
+        self._check_csr(nnz, B, row_ptr, fields, vals)
+        if nnz > self.max_nnz:
+            raise ValueError(f"{nnz} keys in a minibatch, max_nnz is {self.max_nnz}")
+        if B > self.coef.numel():
+            raise ValueError(f"{B} rows in a minibatch, cfg.minibatch is {self.coef.numel()}")
+        loc = self.localizer(keys) if loc is None else loc
+        if self.G == 1:
+            if self.gpu:
+                slot, w_wide = self.shard.resolve(loc.uniq, loc.n_uniq, self.slot_buf, self.w_buf)
+            else:
+                slot, w_wide = self.shard.resolve(loc.uniq[:loc.num_unique()])
+            rows_src, rows_idx = self.shard.rows, slot
+            if self.gpu and cfg.compact_rows:
+                hipops().emb_gather_rows(slot, self.shard.rows, self.rows_u, loc.n_uniq)
+                rows_src, rows_idx = self.rows_u, None
+            push = ("local", slot)
+        else:
+            rows_u, w_wide, push = self._pull(loc)
+            rows_src, rows_idx = rows_u, None
+        if self.gpu:
+            if self.row_of is None:
+                self.row_of = torch.empty(self.max_nnz, dtype=torch.int32, device=self.device)
+            dX0, row_of = self.dX0[:nnz], self.row_of[:nnz]
+            hipops().fwfm_csr(row_ptr, fields, nnz, rows_src, rows_idx, vals, B, self.F, self.R,
+                              loc.local_col, w_wide, labels, self.coef, dX0, row_of, self.dR_part,
+                              self.metrics, self.hist, AUC_BINS)
+            dE = E.grad_reduce(loc, dX0, D, nnz, out=self.dE)
+            l2_cap = nnz if rows_idx is not None else min(nnz, rows_src.shape[0])
+            hipops().fm_l2(dE, rows_src, rows_idx, loc.n_uniq, l2_cap, cfg.lambda_v)
+        else:
+            X0 = E.expand(loc.local_col, nnz, rows_src, idx=rows_idx)
+            row_of = torch.repeat_interleave(torch.arange(B), row_ptr[1:] - row_ptr[:-1])
+            dX0, dR = self._fwd_bwd_torch_csr(X0, vals, row_of, fields, loc.local_col, w_wide,
+                                              labels)
+            self.dR.copy_(dR)
+            U = loc.num_unique()
+            dE = E.grad_reduce(loc, dX0, D, U)
+            v = (rows_src[rows_idx[:U]] if rows_idx is not None else rows_src[:U]).float()
+            dE += cfg.lambda_v * v
+        g_wide, _ = linear_backward(loc, self.coef[:B], B=B, rows=row_of, vals=vals)
+        self._push(loc, push, dE, g_wide)
+        self._update_r()
+        auc_from_hist(self.hist, self.metrics, self.step_dev)
+        self.step_count += 1
+        self.examples += B
+
+    def _forward_math_csr(self, X0, vals, row_of, fld, B, local_col, w_wide, dtype, R=None):
+        """(margin [B], x [nnz] with the fields outside [0, F) masked, x v [nnz, D], the cell
+        row * F + field of every occurrence [nnz], P [B, F, D], T0 [B, F, D], s [B, F],
+        n_f >= 2 ? R[f][f] : 0 [B, F]) in ``dtype``; R is read as symmetric from its upper
+        triangle. Per-row sums are ``index_add`` over ``row_of``; the diagonal acts by select
+        on the row's own count n_f >= 2."""
+        nnz, dev, F = row_of.numel(), X0.device, self.F
+        x = vals[:nnz].to(dtype) if vals is not None else torch.ones(nnz, dtype=dtype, device=dev)
+        ok = (fld[:nnz] >= 0) & (fld[:nnz] < F)
+        xq = torch.where(ok, x, torch.zeros((), dtype=dtype, device=dev))
+        cell = row_of.long() * F + torch.where(ok, fld[:nnz], 0).long()
+        xv = xq[:, None] * X0[:nnz].to(dtype)
+        P = torch.zeros(B * F, xv.shape[1], dtype=dtype, device=dev).index_add_(0, cell, xv)
+        q = torch.zeros(B * F, dtype=dtype, device=dev).index_add_(0, cell, (xv * xv).sum(1))
+        n = torch.zeros(B * F, dtype=dtype, device=dev).index_add_(0, cell, ok.to(dtype))
+        P, pairs = P.view(B, F, -1), (n >= 2).view(B, F)
+        R = (self.R if R is None else R).to(dev, dtype)
+        up = torch.triu(R, 1)
+        T0 = torch.einsum("fg,bgd->bfd", up + up.T, P)
+        zero = torch.zeros((), dtype=dtype, device=dev)
+        s = torch.where(pairs, 0.5 * ((P * P).sum(2) - q.view(B, F)), zero)
+        rsel = torch.where(pairs, torch.diagonal(R)[None, :], zero)
+        lin = torch.zeros(B, dtype=dtype, device=dev).index_add_(
+            0, row_of.long(), w_wide.to(dtype)[local_col[:nnz].long()] * x)
+        m = lin + 0.5 * (P * T0).sum((1, 2)) + (rsel * s).sum(1)
+        return m, xq, xv, cell, P, T0, s, rsel
+
+    def _fwd_bwd_math_csr(self, X0, vals, row_of, fld, local_col, w_wide, labels,
+                          dtype=torch.float32, R=None):
+        """(margin [B], coef [B], dX0 [nnz, D], dR [F, F] symmetric) in ``dtype``, nothing
+        rounded to bf16."""
+        B = labels.numel()
+        m, xq, xv, cell, P, T0, s, rsel = self._forward_math_csr(X0, vals, row_of, fld, B,
+                                                                 local_col, w_wide, dtype, R)
+        y = torch.where(labels > 0, 1.0, -1.0).to(dtype)
+        c = -y * torch.sigmoid(-y * m)
+        D = xv.shape[1]
+        own = rsel.reshape(-1)[cell][:, None] * (P.reshape(-1, D)[cell] - xv)
+        dX = (c[row_of.long()] * xq)[:, None] * (T0.reshape(-1, D)[cell] + own)
+        up = torch.triu(torch.einsum("b,bfd,bgd->fg", c, P, P), 1)
+        return m, c, dX, up + up.T + torch.diag(c @ s)
+
+    def _fwd_bwd_torch_csr(self, X0, vals, row_of, fld, local_col, w_wide, labels,
+                           dtype=torch.float32):
+        """fwfm_csr in PyTorch: the CPU route, and in ``dtype=torch.float64`` the reference
+        the kernel is tested against. ``row_of`` [nnz] is the row of every occurrence (rows in
+        order), ``fld`` [nnz] its field. Returns (dX0 bf16, dR in ``dtype``)."""
+        m, c, dX, dR = self._fwd_bwd_math_csr(X0, vals, row_of, fld, local_col, w_wide, labels,
+                                              dtype)
+        return self._account(m, c, dX, labels, labels.numel()), dR
+
     # ------------------------------------------------------------------ eval
-    def predict(self, keys: torch.Tensor, B: int, vals: torch.Tensor | None = None):
+    def predict(self, keys: torch.Tensor, B: int, vals: torch.Tensor | None = None,
+                row_ptr: torch.Tensor | None = None, fields: torch.Tensor | None = None):
         """Margins of B examples (no update, no insert; unseen keys contribute 0). G == 1.
-        A GPU trainer scores with the forward-only kernel (``fwfm_margins``), slots and wide
-        weights per occurrence."""
+        Rows of ``cfg.slots`` keys, or CSR rows with ``row_ptr`` [B + 1] and ``fields`` [nnz]
+        as ``step``. A GPU trainer scores with the forward-only kernels (``fwfm_margins`` /
+        ``fwfm_csr_margins``), slots and wide weights per occurrence."""
         if self.G != 1:
             raise NotImplementedError("predict() reads the local shard (G == 1)")
         from ..ops.keymix import mix
 
         S = self.cfg.slots
         nnz = keys.numel()
-        if nnz != B * S:
+        csr = row_ptr is not None or fields is not None
+        if csr:
+            self._check_csr(nnz, B, row_ptr, fields, vals)
+        elif nnz != B * S:
             raise ValueError(f"expected {B * S} keys, got {nnz}")
         mk = mix(keys.to(self.device), self.bits)
         slot, w = self.shard.table.resolve(mk, insert=False)
@@ -263,11 +400,19 @@ class FwFMTrainer(EmbeddingPS):
         w = torch.where(ok, w, torch.zeros_like(w))
         if self.gpu:
             margins = torch.empty(B, dtype=torch.float32, device=self.device)
-            hipops().fwfm_margins(self.shard.rows, slot, vals, B, S, self.fields, self.F, self.R,
-                                  None, w, margins)
+            if csr:
+                hipops().fwfm_csr_margins(row_ptr, fields, nnz, self.shard.rows, slot, vals, B,
+                                          self.F, self.R, None, w, margins)
+            else:
+                hipops().fwfm_margins(self.shard.rows, slot, vals, B, S, self.fields, self.F,
+                                      self.R, None, w, margins)
             return margins
         X0 = torch.zeros(nnz, self.cfg.embedding_dim, device=self.device)
         X0[ok] = self.shard.rows[slot[ok]].float()
+        if csr:
+            r = torch.repeat_interleave(torch.arange(B), row_ptr[1:] - row_ptr[:-1])
+            return self._forward_math_csr(X0, vals, r, fields, B, torch.arange(nnz), w,
+                                          torch.float32)[0]
         return self._forward_math(X0, vals, B, S, torch.arange(nnz), w, torch.float32)[0]
 
     progress = FMTrainer.progress
