@@ -206,6 +206,103 @@ def ffm_score_mode(args):
         **res}), flush=True)
 
 
+def fwfm_score_mode(args):
+    """1 GPU: scoring held-out minibatches against a field-weighted FM (D = 16, F = 39) with the
+    fused kernel (``FwFMTrainer.scorer()``: fwfm_predict.hip, margins only and labels +
+    accumulator) and with the composed route (``FwFMTrainer.predict``: mix, resolve, where, then
+    fwfm_margins or fwfm_csr_margins), alternated window by window in this one process on a
+    table filled by a few training steps. Shapes: Criteo's B x 39 fixed rows; the same rows as
+    CSR with a quarter of the slots missing; CSR rows of which a quarter are widened to 65..130
+    occurrences. Per route and window: a host clock around the synchronised window, and device
+    events around the same launches (for the fused routes, one kernel per minibatch: the
+    kernel's own time)."""
+    from parameter_server_amd.models.fwfm import FwFMConfig, FwFMTrainer
+    from parameter_server_amd.ops.synthetic import criteo_batch
+
+    dev = torch.device("cuda", 0)
+    B, N, S = args.minibatch, int(args.num_features), 39
+    tr = FwFMTrainer(FwFMConfig(embedding_dim=16, localize=args.localize, num_features=N,
+                                minibatch=B, table_capacity=min(args.table_slots, 1 << 24),
+                                seed=0), device=dev)
+    crit = [criteo_batch(B, seed=77, row0=i * B, num_features=N, device=dev)
+            for i in range(args.train_steps + 4)]
+    for i in range(args.train_steps):
+        tr.step(*crit[i])
+    sc = tr.scorer()
+    g = torch.Generator(device=dev).manual_seed(5)
+    slot_of = torch.arange(S, dtype=torch.int32, device=dev).repeat(B)
+    fixed, missing, wide = [], [], []
+    for k39, y in crit[args.train_steps:]:
+        fixed.append((k39, y, dict(width=S), {}))
+        keep = torch.rand(B * S, device=dev, generator=g) < 0.75
+        rp = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        rp[1:] = torch.cumsum(keep.view(B, S).sum(1), 0)
+        kw = dict(row_ptr=rp, fields=slot_of[keep])
+        missing.append((k39[keep], y, kw, kw))
+        # a quarter of the rows take the keys of the rows after them (fields repeat there:
+        # the diagonal of R acts), as --fwfm's wide route
+        width = torch.where(torch.rand(B, device=dev, generator=g) < 0.25,
+                            torch.randint(65, 131, (B,), device=dev, generator=g), S)
+        rp = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        rp[1:] = torch.cumsum(width, 0)
+        row = torch.repeat_interleave(torch.arange(B, device=dev), width)
+        pos = torch.arange(int(rp[-1]), device=dev) - rp[row]
+        kw = dict(row_ptr=rp, fields=(pos % S).int())
+        wide.append((k39.view(B, S)[(row + pos // S) % B, pos % S].contiguous(), y, kw, kw))
+
+    def measure(tag, held, n):
+        """held: (keys, labels, the scorer's keywords, predict's keywords)"""
+        routes = {"fused_margins": lambda b: sc.predict(b[0], **b[2]),
+                  "fused_labels_acc": lambda b: sc.score(b[0], b[1], margins=False, **b[2]),
+                  "composed_predict": lambda b: tr.predict(b[0], B, **b[3])}
+        a, c = routes["fused_margins"](held[0]), routes["composed_predict"](held[0])
+        print(f"{tag}: max |fused - composed| margin = {float((a - c).abs().max()):.3g}, "
+              f"max |margin| = {float(c.abs().max()):.3g}", flush=True)
+        host, devt = {r: [] for r in routes}, {r: [] for r in routes}
+        for fn in routes.values():
+            for i in range(args.warmup):
+                fn(held[i % len(held)])
+        for r in range(max(args.repeats, 5)):
+            for name, fn in routes.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e0.record()
+                for i in range(n):
+                    fn(held[i % len(held)])
+                e1.record()
+                torch.cuda.synchronize()
+                host[name].append((time.perf_counter() - t0) / n * 1e3)
+                devt[name].append(e0.elapsed_time(e1) / n)
+            print(f"{tag} window {r}: " + "  ".join(
+                f"{k} {host[k][-1]:.4f} ms (events {devt[k][-1]:.4f})" for k in routes), flush=True)
+        med = lambda d: {k: sorted(v)[len(v) // 2] for k, v in d.items()}
+        span = lambda d: {k: [min(v), max(v)] for k, v in d.items()}
+        mh, md = med(host), med(devt)
+        return {"rows": B, "nnz": held[0][0].numel(), "minibatches_per_window": n,
+                "median_ms": mh, "min_max_ms": span(host), "median_event_ms": md,
+                "min_max_event_ms": span(devt),
+                "composed_over_fused_margins": mh["composed_predict"] / mh["fused_margins"],
+                "composed_over_fused_margins_events":
+                    md["composed_predict"] / md["fused_margins"]}
+
+    n = max(args.steps, 100)
+    res = {"criteo_fixed_39": measure("criteo fixed", fixed, n),
+           "criteo_csr_quarter_missing": measure("criteo csr missing", missing, n),
+           "csr_quarter_wide_65_130": measure("csr quarter wide", wide, n)}
+    occ, _ = tr.shard.table.census()
+    print(json.dumps({
+        "metric": "FwFM scoring time per minibatch, fused kernel (FwFMScorer) vs "
+                  "FwFMTrainer.predict, 1 GPU, F = 39, D = 16",
+        "unit": "ms/minibatch (median of windows)", "windows": max(args.repeats, 5),
+        "minibatch": B, "train_steps": args.train_steps, "keys_in_table": occ,
+        "table_slots": tr.shard.capacity, "eval": sc.result(),
+        "R_min_max": [float(tr.R.min()), float(tr.R.max())],
+        "not_measured": ["per-phase cycles", "other D and F", "a table that misses L2",
+                         "other gang sizes and waves per block than the launcher's"],
+        **res}), flush=True)
+
+
 def csr_mode(args):
     """1 GPU: the same Criteo-shaped minibatches through the fixed-width step and through the
     ``row_ptr`` step (fm_csr), alternated window by window in this one process, then an
@@ -454,6 +551,10 @@ def main():
     ap.add_argument("--fwfm", action="store_true",
                     help="1 GPU: the field-weighted FM step (D = 16, F = 39) vs the FM step at "
                          "D = 16 and the FFM step at k = 2, alternated")
+    ap.add_argument("--fwfm-score", action="store_true",
+                    help="1 GPU: the fused FwFM scorer (FwFMScorer, D = 16, F = 39) vs "
+                         "FwFMTrainer.predict on fixed rows, CSR rows with slots missing and CSR "
+                         "rows of which a quarter are wider than 64, alternated")
     ap.add_argument("--ffm", action="store_true",
                     help="1 GPU: the field-aware FM step (k = 2, and k = 4 on 27 fields) vs the same "
                          "step with the PyTorch forward / backward and the FM step, alternated")
@@ -481,6 +582,8 @@ def main():
     ap.add_argument("--prefetch", type=int, default=1,
                     help="generate + localise minibatch t+1 on a side stream during step t")
     args = ap.parse_args()
+    if args.fwfm_score:
+        return fwfm_score_mode(args)
     if args.fwfm:
         return fwfm_mode(args)
     if args.ffm and args.score:

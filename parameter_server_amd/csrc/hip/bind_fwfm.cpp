@@ -1,6 +1,8 @@
-// Bindings of the field-weighted factorization machine (fwfm.hip, fwfm_csr.hip).
+// Bindings of the field-weighted factorization machine (fwfm.hip, fwfm_csr.hip) and of its
+// stored-model scoring (fwfm_predict.hip).
 #include "bind_common.h"
 #include "fwfm.h"
+#include "fwfm_predict.h"
 
 using namespace psamd_bind;
 
@@ -213,4 +215,51 @@ void psamd_bind::register_fwfm(py::module_& m) {
   }, py::arg("dR_part"), py::arg("dR"), py::arg("F"), py::arg("sum"), py::arg("update"),
      py::arg("R") = py::none(), py::arg("acc") = py::none(), py::arg("lr") = 0.0,
      py::arg("lambda_r") = 0.0);
+  // Scoring a stored FwFM from raw keys (fwfm_predict.hip), the arguments of ffm_predict_rows
+  // with R [F, F] f32 in the place of k: with row_ptr, fields [nnz] int32 (one per
+  // occurrence); with a fixed width, field_of [width] int32 (position -> field; None: the
+  // position is the field). metrics / hist need labels.
+  m.def("fwfm_predict_rows", [](Tensor slots, uint64_t home_base, uint64_t home_m, Tensor rows,
+                                Tensor keys, int bits, int F, Tensor R, optional<Tensor> row_ptr,
+                                int width, optional<Tensor> fields, optional<Tensor> field_of,
+                                optional<Tensor> vals, optional<Tensor> labels, int64_t B,
+                                int loss_type, optional<Tensor> margin, optional<Tensor> metrics,
+                                optional<Tensor> hist, int nbins) {
+    const std::string op = "fwfm_predict_rows: ";
+    const psamd::TableRef t = table_ref(slots, home_base, home_m);
+    chk(rows, at::kBFloat16, "rows");
+    chk(keys, at::kLong, "keys");
+    chk(R, at::kFloat, "R");
+    check(rows.dim() == 2 && rows.size(0) == t.cap, op + "rows must be [table capacity, D]");
+    check(F >= 1 && F <= 64 && R.numel() == (int64_t)F * F, op + "R [F, F], 1..64 fields");
+    const int64_t nnz = keys.numel();
+    check(B >= 0, op + "B >= 0");
+    const int64_t* rp = optr<int64_t>(row_ptr, at::kLong, "row_ptr");
+    if (rp) check(row_ptr->numel() >= B + 1, "row_ptr too small");
+    else check(width > 0 && B <= nnz / width, "fixed width layout too small");
+    const int32_t* fl = optr<int32_t>(fields, at::kInt, "fields");
+    if (fl) check(fields->numel() >= nnz, "fields too small");
+    const int32_t* fo = optr<int32_t>(field_of, at::kInt, "field_of");
+    const float* v = optr<float>(vals, at::kFloat, "vals");
+    if (v) check(vals->numel() >= nnz, "vals too small");
+    const float* lb = optr<float>(labels, at::kFloat, "labels");
+    if (lb) check(labels->numel() >= B, "labels too small");
+    float* mg = optr<float>(margin, at::kFloat, "margin");
+    if (mg) check(margin->numel() >= B, "margin too small");
+    const psamd::StripedAcc acc = striped_acc(metrics, "metrics");
+    if (acc.ptr) check(lb && metrics->numel() >= 3, "metrics needs labels and >= 3 slots");
+    auto* hp = optr<unsigned long long>(hist, at::kLong, "hist");
+    if (hp) check(lb && nbins > 0 && nbins <= 8192 && hist->numel() >= 2 * nbins &&
+                      hist->numel() % (2 * nbins) == 0,
+                  "hist needs labels and int64 [stripes x 2 x nbins], nbins <= 8192");
+    check(loss_type >= 1 && loss_type <= 4, "loss type in [1, 4]");
+    psamd::fwfm_predict_rows(t, make_keymix(bits), rows.data_ptr(), (int)rows.size(1), F,
+                             ptr<float>(R), ptr<uint64_t>(keys), nnz, rp, width, fl, fo,
+                             fo ? field_of->numel() : 0, v, lb, B, loss_type, mg, acc, hp, nbins,
+                             hp ? (int)(hist->numel() / (2 * nbins)) : 1, cur_stream());
+  }, py::arg("slots"), py::arg("home_base"), py::arg("home_m"), py::arg("rows"), py::arg("keys"),
+     py::arg("bits"), py::arg("F"), py::arg("R"), py::arg("row_ptr"), py::arg("width"),
+     py::arg("fields"), py::arg("field_of"), py::arg("vals"), py::arg("labels"), py::arg("B"),
+     py::arg("loss_type"), py::arg("margin"), py::arg("metrics"), py::arg("hist"),
+     py::arg("nbins"));
 }

@@ -33,7 +33,12 @@ which on rows of one width and one map is the model above. The step is ``FFMTrai
 sequence with ``fwfm_csr`` (fwfm_csr.hip: one kernel for every width, a row walked in rounds
 of 64 occurrences) in the middle and the same reduce + update of R after it.
 
-Not here yet: a fused table-probe scorer and the app's ``.conf`` route.
+``scorer()`` gives an ``FwFMScorer`` (models/scorer.py) on the trainer's own shard and live R:
+margins, loss / accuracy sums and the AUC histogram of held-out rows in one launch per
+minibatch (fwfm_predict.hip); ``FwFMScorer.from_state_dict`` scores a snapshot of any world
+size.
+
+Not here yet: the app's ``.conf`` route.
 """
 from __future__ import annotations
 
@@ -49,6 +54,7 @@ from ..ops.kv_table import UpdateRule, next_pow2
 from ..ops.linear import AUC_BINS, auc_from_hist, linear_backward, new_accum
 from ..ops.localize import Localizer
 from ..ops.native import hipops
+from ..ops.score import fwfm_forward, fwfm_forward_csr
 from ..parallel.comm import Comm, LocalComm
 from ..parallel.partition import KeyPartition
 from .ffm import FFMTrainer
@@ -224,23 +230,8 @@ class FwFMTrainer(EmbeddingPS):
     def _forward_math(self, X0, vals, B, S, local_col, w_wide, dtype, R=None):
         """(margin [B], x [B, S], x v [B, S, D], P [B, F, D], q [B, F], T [B, F, D], diag R
         [F]) in ``dtype``; R is read as symmetric from its upper triangle."""
-        dev, F = X0.device, self.F
-        x = (vals[:B * S].to(dtype) if vals is not None else
-             torch.ones(B * S, dtype=dtype, device=dev)).reshape(B, S)
-        xv = x[..., None] * X0[:B * S].to(dtype).reshape(B, S, -1)
-        onehot = torch.zeros(S, F, dtype=dtype, device=dev)
-        onehot[torch.arange(S, device=dev), self._fields_t.to(dev)] = 1
-        P = torch.einsum("sf,bsd->bfd", onehot, xv)
-        q = (xv * xv).sum(2) @ onehot
-        R = (self.R if R is None else R).to(dev, dtype)
-        # a field of fewer than two positions has no same-field pair: its diagonal entry
-        # has no part in the model and is read as 0
-        rd = torch.diagonal(R) * (onehot.sum(0) >= 2)
-        Rs = torch.triu(R, 1) + torch.triu(R, 1).T + torch.diag(rd)
-        T = torch.einsum("fg,bgd->bfd", Rs, P)
-        lc = local_col[:B * S].long().reshape(B, S)
-        m = (w_wide.to(dtype)[lc] * x).sum(1) + 0.5 * ((P * T).sum((1, 2)) - q @ rd)
-        return m, x, xv, P, q, T, rd
+        return fwfm_forward(X0, vals, B, S, self._fields_t, self.F, self.R if R is None else R,
+                            local_col, w_wide, dtype)
 
     def _fwd_bwd_math(self, X0, vals, B, S, local_col, w_wide, labels, dtype=torch.float32,
                       R=None):
@@ -326,31 +317,10 @@ class FwFMTrainer(EmbeddingPS):
         self.examples += B
 
     def _forward_math_csr(self, X0, vals, row_of, fld, B, local_col, w_wide, dtype, R=None):
-        """(margin [B], x [nnz] with the fields outside [0, F) masked, x v [nnz, D], the cell
-        row * F + field of every occurrence [nnz], P [B, F, D], T0 [B, F, D], s [B, F],
-        n_f >= 2 ? R[f][f] : 0 [B, F]) in ``dtype``; R is read as symmetric from its upper
-        triangle. Per-row sums are ``index_add`` over ``row_of``; the diagonal acts by select
-        on the row's own count n_f >= 2."""
-        nnz, dev, F = row_of.numel(), X0.device, self.F
-        x = vals[:nnz].to(dtype) if vals is not None else torch.ones(nnz, dtype=dtype, device=dev)
-        ok = (fld[:nnz] >= 0) & (fld[:nnz] < F)
-        xq = torch.where(ok, x, torch.zeros((), dtype=dtype, device=dev))
-        cell = row_of.long() * F + torch.where(ok, fld[:nnz], 0).long()
-        xv = xq[:, None] * X0[:nnz].to(dtype)
-        P = torch.zeros(B * F, xv.shape[1], dtype=dtype, device=dev).index_add_(0, cell, xv)
-        q = torch.zeros(B * F, dtype=dtype, device=dev).index_add_(0, cell, (xv * xv).sum(1))
-        n = torch.zeros(B * F, dtype=dtype, device=dev).index_add_(0, cell, ok.to(dtype))
-        P, pairs = P.view(B, F, -1), (n >= 2).view(B, F)
-        R = (self.R if R is None else R).to(dev, dtype)
-        up = torch.triu(R, 1)
-        T0 = torch.einsum("fg,bgd->bfd", up + up.T, P)
-        zero = torch.zeros((), dtype=dtype, device=dev)
-        s = torch.where(pairs, 0.5 * ((P * P).sum(2) - q.view(B, F)), zero)
-        rsel = torch.where(pairs, torch.diagonal(R)[None, :], zero)
-        lin = torch.zeros(B, dtype=dtype, device=dev).index_add_(
-            0, row_of.long(), w_wide.to(dtype)[local_col[:nnz].long()] * x)
-        m = lin + 0.5 * (P * T0).sum((1, 2)) + (rsel * s).sum(1)
-        return m, xq, xv, cell, P, T0, s, rsel
+        """ops/score.py ``fwfm_forward_csr`` (shared with ``fwfm_score``'s CPU path) on this
+        trainer's F and R."""
+        return fwfm_forward_csr(X0, vals, row_of, fld, B, self.F, self.R if R is None else R,
+                                local_col, w_wide, dtype)
 
     def _fwd_bwd_math_csr(self, X0, vals, row_of, fld, local_col, w_wide, labels,
                           dtype=torch.float32, R=None):
@@ -414,5 +384,19 @@ class FwFMTrainer(EmbeddingPS):
             return self._forward_math_csr(X0, vals, r, fields, B, torch.arange(nnz), w,
                                           torch.float32)[0]
         return self._forward_math(X0, vals, B, S, torch.arange(nnz), w, torch.float32)[0]
+
+    def scorer(self):
+        """An ``FwFMScorer`` on this trainer's own shard and R (no copy: later steps stay
+        visible), with ``cfg.fields`` as its position -> field map: held-out loss, accuracy
+        and AUC through the fused scoring kernel, rows of any width. G == 1. Nothing is
+        synchronised here: score on the stream the steps run on, after them."""
+        if self.G != 1:
+            raise NotImplementedError(
+                "scorer() reads the local shard (G == 1); score a sharded model with "
+                "FwFMScorer.from_state_dict(FwFMTrainer.merge_state_dicts(<every rank's "
+                "state_dict()>), device)")
+        from .scorer import FwFMScorer
+
+        return FwFMScorer.from_shard(self.shard, self.bits, self.F, self.R, fields=self.fields)
 
     progress = FMTrainer.progress

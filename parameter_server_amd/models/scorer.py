@@ -15,7 +15,8 @@ import torch
 from ..ops.embedding import EmbeddingShard
 from ..ops.keymix import mix
 from ..ops.kv_table import KVTable, next_pow2
-from ..ops.score import ScoreAccum, auc_from_counts, ffm_score, fm_score, score
+from ..ops.score import (ScoreAccum, auc_from_counts, ffm_score, fm_score, fwfm_score,
+                         score)
 
 
 class ModelScorer:
@@ -257,5 +258,86 @@ class FFMScorer(ModelScorer):
         """One fixed-width ``DeviceBatch`` of a ``DeviceFeeder``, through the position map."""
         if b.row_ptr is not None:
             raise ValueError("FFMScorer.score_batch: a CSR DeviceBatch carries no field ids; "
+                             "score CSR rows with score(keys, labels, row_ptr=, fields=)")
+        return super().score_batch(b, margins)
+
+
+class FwFMScorer(ModelScorer):
+    """``ModelScorer`` for a field-weighted factorization machine (models/fwfm.py): the model
+    is an ``EmbeddingShard`` with one vector of 8, 16 or 32 bf16 per key and ``R``, the float32
+    [F, F] field-pair strengths, held by reference (a trainer's live R stays visible, nothing is
+    copied per call). Every minibatch is one launch of the fused probe + Gram-tile kernel
+    (ops/score.py ``fwfm_score``, csrc/hip/fwfm_predict.hip), for rows of any width.
+    ``fields``: the position -> field map of fixed-width rows (None: identity), uploaded once.
+    CSR rows bring ``fields=`` [nnz] int32, the field of every occurrence, with each call.
+    ``evaluate``, ``totals`` and ``result`` are ``ModelScorer``'s."""
+
+    def __init__(self, shard: EmbeddingShard, bits: int, num_fields: int, R: torch.Tensor,
+                 fields=None, loss="logit"):
+        super().__init__(shard.table, bits, loss)
+        self.shard, self.F, self.R = shard, int(num_fields), R
+        if not 1 <= self.F <= 64 or shard.dim not in (8, 16, 32):
+            raise ValueError(f"{self.F} fields (1..64) on rows of {shard.dim} columns (8, 16 or "
+                             "32) are outside the FwFM's geometry")
+        if not isinstance(R, torch.Tensor) or R.dtype != torch.float32 or \
+                tuple(R.shape) != (self.F, self.F) or R.device.type != self.device.type:
+            raise ValueError(f"R must be a float32 [{self.F}, {self.F}] tensor on {self.device}")
+        self.fields = None if fields is None else [int(f) for f in fields]
+        if self.fields and not 0 <= min(self.fields) <= max(self.fields) < self.F:
+            raise ValueError(f"every field must lie in [0, {self.F})")
+        self._field_of = None if self.fields is None else \
+            torch.tensor(self.fields, dtype=torch.int32, device=self.device)
+
+    @classmethod
+    def from_shard(cls, shard: EmbeddingShard, bits: int, num_fields: int, R: torch.Tensor,
+                   fields=None, loss="logit") -> "FwFMScorer":
+        """Alias an existing shard and R (no copy). The caller orders its own updates before
+        the scoring launches (``FwFMTrainer.scorer``: the same stream)."""
+        return cls(shard, bits, num_fields, R, fields, loss)
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, device, fields=None,
+                        capacity: int | None = None) -> "FwFMScorer":
+        """A snapshot of ``FwFMTrainer.state_dict`` (or ``merge_state_dicts`` of the ranks'
+        snapshots: R is replicated, the keys are raw ids) in a shard of its own at load <= 0.5;
+        F and R come from ``sd["R"]``, key width and factor dimension from the snapshot, which
+        does not record the position -> field map: ``fields`` is the trainer's."""
+        if str(sd.get("model")) != "FwFMTrainer":
+            raise ValueError(f"snapshot of a {sd.get('model')}, not an FwFMTrainer")
+        bits, dim = int(sd["bits"]), int(sd["dim"])
+        R = sd["R"].to(device=device, dtype=torch.float32).contiguous()
+        n = sd["keys"].numel()
+        shard = EmbeddingShard(capacity or next_pow2(max(64, 2 * n)), dim, device)
+        if n:  # (check_ok inside: a capacity too small raises 'KVTable full')
+            mk = mix(sd["keys"].cpu().contiguous(), bits)
+            shard.load_state(mk, sd["w"], sd["z"], sd["n"], sd["rows"], sd["acc"],
+                             cnt=sd.get("cnt"))
+        return cls(shard, bits, R.shape[0], R, fields)
+
+    def _score(self, keys, fields=None, **kw):
+        if kw.get("row_ptr") is None:
+            if fields is not None:
+                raise ValueError("fixed-width rows use the scorer's position -> field map; "
+                                 "fields= is the field of every occurrence of CSR rows")
+            fields = self._field_of
+        return fwfm_score(self.shard, keys, self.bits, num_fields=self.F, R=self.R,
+                          fields=fields, **kw)
+
+    def predict(self, keys: torch.Tensor, *, row_ptr=None, width=None, vals=None,
+                fields=None) -> torch.Tensor:
+        """Margins only (nothing accumulated)."""
+        return self._score(keys, fields, row_ptr=row_ptr, width=width, vals=vals)
+
+    def score(self, keys, labels, *, row_ptr=None, width=None, vals=None, fields=None,
+              margins=True):
+        """Margins of one labelled minibatch; its sums and bins go into the accumulator."""
+        B = row_ptr.numel() - 1 if row_ptr is not None else keys.numel() // int(width)
+        return self._score(keys, fields, row_ptr=row_ptr, width=width, vals=vals, labels=labels,
+                           margins=margins, acc=self.acc, loss=self.loss, B=B)
+
+    def score_batch(self, b, margins: bool = False):
+        """One fixed-width ``DeviceBatch`` of a ``DeviceFeeder``, through the position map."""
+        if b.row_ptr is not None:
+            raise ValueError("FwFMScorer.score_batch: a CSR DeviceBatch carries no field ids; "
                              "score CSR rows with score(keys, labels, row_ptr=, fields=)")
         return super().score_batch(b, margins)

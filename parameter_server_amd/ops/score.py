@@ -289,6 +289,145 @@ def ffm_score(shard, keys: torch.Tensor, bits: int, *, num_fields: int, k: int, 
     return m if margins else None
 
 
+def fwfm_forward(X0, vals, B: int, S: int, fl, F: int, R, local_col, w_wide, dtype):
+    """The field-weighted FM's forward on fixed-width rows in PyTorch (``FwFMTrainer``'s CPU
+    route and float64 reference, and ``fwfm_score``'s CPU path): expanded rows X0 [B*S, D],
+    ``fl`` [S] (long) position -> field in [0, F). Returns (margin [B], x [B, S], x v
+    [B, S, D], P [B, F, D], q [B, F], T [B, F, D], diag R [F]) in ``dtype``; R is read as
+    symmetric from its upper triangle."""
+    dev = X0.device
+    x = (vals[:B * S].to(dtype) if vals is not None else
+         torch.ones(B * S, dtype=dtype, device=dev)).reshape(B, S)
+    xv = x[..., None] * X0[:B * S].to(dtype).reshape(B, S, -1)
+    onehot = torch.zeros(S, F, dtype=dtype, device=dev)
+    onehot[torch.arange(S, device=dev), fl.to(dev)] = 1
+    P = torch.einsum("sf,bsd->bfd", onehot, xv)
+    q = (xv * xv).sum(2) @ onehot
+    R = R.to(dev, dtype)
+    # a field of fewer than two positions has no same-field pair: its diagonal entry
+    # has no part in the model and is read as 0
+    rd = torch.diagonal(R) * (onehot.sum(0) >= 2)
+    Rs = torch.triu(R, 1) + torch.triu(R, 1).T + torch.diag(rd)
+    T = torch.einsum("fg,bgd->bfd", Rs, P)
+    lc = local_col[:B * S].long().reshape(B, S)
+    m = (w_wide.to(dtype)[lc] * x).sum(1) + 0.5 * ((P * T).sum((1, 2)) - q @ rd)
+    return m, x, xv, P, q, T, rd
+
+
+def fwfm_forward_csr(X0, vals, row_of, fld, B: int, F: int, R, local_col, w_wide, dtype):
+    """The field-weighted FM's forward on CSR rows with a field per occurrence, in PyTorch
+    (``FwFMTrainer``'s CPU route and float64 reference, and ``fwfm_score``'s CPU path):
+    (margin [B], x [nnz] with the fields outside [0, F) masked, x v [nnz, D], the cell
+    row * F + field of every occurrence [nnz], P [B, F, D], T0 [B, F, D], s [B, F],
+    n_f >= 2 ? R[f][f] : 0 [B, F]) in ``dtype``; R is read as symmetric from its upper
+    triangle. Per-row sums are ``index_add`` over ``row_of``; the diagonal acts by select
+    on the row's own count n_f >= 2."""
+    nnz, dev = row_of.numel(), X0.device
+    x = vals[:nnz].to(dtype) if vals is not None else torch.ones(nnz, dtype=dtype, device=dev)
+    ok = (fld[:nnz] >= 0) & (fld[:nnz] < F)
+    xq = torch.where(ok, x, torch.zeros((), dtype=dtype, device=dev))
+    cell = row_of.long() * F + torch.where(ok, fld[:nnz], 0).long()
+    xv = xq[:, None] * X0[:nnz].to(dtype)
+    P = torch.zeros(B * F, xv.shape[1], dtype=dtype, device=dev).index_add_(0, cell, xv)
+    q = torch.zeros(B * F, dtype=dtype, device=dev).index_add_(0, cell, (xv * xv).sum(1))
+    n = torch.zeros(B * F, dtype=dtype, device=dev).index_add_(0, cell, ok.to(dtype))
+    P, pairs = P.view(B, F, -1), (n >= 2).view(B, F)
+    R = R.to(dev, dtype)
+    up = torch.triu(R, 1)
+    T0 = torch.einsum("fg,bgd->bfd", up + up.T, P)
+    zero = torch.zeros((), dtype=dtype, device=dev)
+    s = torch.where(pairs, 0.5 * ((P * P).sum(2) - q.view(B, F)), zero)
+    rsel = torch.where(pairs, torch.diagonal(R)[None, :], zero)
+    lin = torch.zeros(B, dtype=dtype, device=dev).index_add_(
+        0, row_of.long(), w_wide.to(dtype)[local_col[:nnz].long()] * x)
+    m = lin + 0.5 * (P * T0).sum((1, 2)) + (rsel * s).sum(1)
+    return m, xq, xv, cell, P, T0, s, rsel
+
+
+def fwfm_score(shard, keys: torch.Tensor, bits: int, *, num_fields: int, R: torch.Tensor,
+               row_ptr=None, width=None, fields=None, vals=None, labels=None,
+               margins: bool = True, acc: ScoreAccum | None = None, loss="logit",
+               B: int | None = None):
+    """``score`` for a field-weighted factorization machine: ``shard`` is an ``EmbeddingShard``
+    with one vector of ``dim`` in {8, 16, 32} bf16 per key (models/fwfm.py), ``R`` the float32
+    [F, F] field-pair strengths on the keys' device, read as symmetric from its upper triangle;
+    margin = x.w + sum_{i<j} x_i x_j R[f_i][f_j] <v_i, v_j>, a key the model does not hold
+    contributing nothing. The field arguments are ``ffm_score``'s: with ``row_ptr``, ``fields``
+    is int32 [nnz], the field of every occurrence (one outside [0, F) keeps its linear term and
+    enters no pair); with a fixed ``width`` it is the position -> field map (int32 [width] on
+    the keys' device, or a list; None: identity).
+    GPU: one ``fwfm_predict_rows`` launch (csrc/hip/fwfm_predict.hip), rows of any width; CPU:
+    the PyTorch ops of ``FwFMTrainer.predict`` in f32 (``fwfm_forward_csr``, and
+    ``fwfm_forward`` for a fixed width: on one map the same model, summed as the trainer's
+    fixed-width route sums it, so a scorer and its trainer agree to the bit)."""
+    if (row_ptr is None) == (not width):
+        raise ValueError("fwfm_score needs row_ptr or a fixed width, not both")
+    if acc is not None and labels is None:
+        raise ValueError("fwfm_score: an accumulator needs labels")
+    F = int(num_fields)
+    if not 1 <= F <= 64 or shard.dim not in (8, 16, 32):
+        raise ValueError(f"fwfm_score: {F} fields (1..64) on rows of {shard.dim} columns "
+                         "(8, 16 or 32)")
+    if not isinstance(R, torch.Tensor) or R.dtype != torch.float32 or tuple(R.shape) != (F, F) \
+            or not R.is_contiguous():
+        raise ValueError(f"fwfm_score: R must be a contiguous float32 [{F}, {F}] tensor")
+    keys = keys.contiguous()
+    nnz = keys.numel()
+    dev = keys.device
+    if R.device.type != dev.type:
+        raise ValueError(f"fwfm_score: R must be on the keys' device ({dev})")
+    if row_ptr is not None:
+        if fields is None or not isinstance(fields, torch.Tensor) or \
+                fields.dtype != torch.int32 or fields.numel() != nnz:
+            raise ValueError(f"fwfm_score: rows by row_ptr need fields, int32 [{nnz}]")
+    elif fields is None:
+        if int(width) > F:
+            raise ValueError(f"fwfm_score: rows of {int(width)} positions on {F} fields need a "
+                             "position -> field map")
+    else:
+        if not isinstance(fields, torch.Tensor):
+            fields = torch.tensor([int(f) for f in fields], dtype=torch.int32, device=dev)
+        if fields.dtype != torch.int32 or fields.numel() != int(width):
+            raise ValueError(f"fwfm_score: the position -> field map must be int32 [{int(width)}]")
+    if fields is not None and fields.device.type != dev.type:
+        raise ValueError(f"fwfm_score: fields must be on the keys' device ({dev})")
+    if B is None:
+        B = row_ptr.numel() - 1 if row_ptr is not None else nnz // int(width)
+    L = loss_id(loss)
+    table = shard.table
+    if is_gpu(keys):
+        m = torch.empty(B, dtype=torch.float32, device=dev) if margins else None
+        if B:
+            csr = row_ptr is not None
+            hipops().fwfm_predict_rows(table.slots, table.home_base, table.home_m, shard.rows,
+                                       keys, bits, F, R, row_ptr, int(width or 0),
+                                       fields if csr else None, None if csr else fields, vals,
+                                       labels, B, L, m, acc.metrics if acc is not None else None,
+                                       acc.hist if acc is not None else None, AUC_BINS)
+        return m
+    if B == 0:
+        return torch.empty(0, dtype=torch.float32) if margins else None
+    slot, w = table.resolve(mix(keys, bits), insert=False)
+    ok = slot >= 0
+    w = torch.where(ok, w, torch.zeros_like(w))
+    X0 = torch.zeros(nnz, shard.dim, device=dev)
+    X0[ok] = shard.rows[slot[ok]].float()
+    if row_ptr is not None:
+        r = torch.repeat_interleave(torch.arange(B), row_ptr[1:B + 1] - row_ptr[:B])
+        n = r.numel()
+        m = fwfm_forward_csr(X0[:n], vals, r, fields, B, F, R, torch.arange(n), w,
+                             torch.float32)[0]
+    else:
+        S = int(width)
+        fl = torch.arange(S) if fields is None else fields.long()
+        if int(fl.min()) < 0 or int(fl.max()) >= F:
+            raise ValueError(f"fwfm_score: every field of the position map must lie in [0, {F})")
+        m = fwfm_forward(X0, vals, B, S, fl, F, R, torch.arange(B * S), w, torch.float32)[0]
+    if acc is not None:
+        _accumulate(acc, m, labels, B, L)
+    return m if margins else None
+
+
 def row_bound(keys: torch.Tensor, w_of: dict, vals=None, row_ptr=None, width=None):
     """fp64 reference margins by a dictionary loop over the raw keys (no mixing, no table)
     and the derived f32 bound per row, (n_r + 2) 2^-23 sum |w x|: n_r products rounded once
